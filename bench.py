@@ -8,8 +8,15 @@ batch: forward, BCE, backward, dense-exact Adam over all 140.8M embedding parame
 parameters (src/model/trainer.py:253-285).  Synthetic data: users uniform, positive items
 Zipf(1.05), negatives uniform; random-init weights.  Inputs are resident in HBM before timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run sets up, primes and warms up, times the K steps and prints the headline (``value``
+= train samples/s over the K timed steps, ``ms_per_step`` = milliseconds per timed step).
+``--full`` then runs every other section on the same model (the 8-batch cycle, per-launch
+profiles and rooflines, inference, the reference call pattern, bf16 tables, B=256, C1, the
+large-batch embedding line, C4, C5 scoring, the CPU baselines) and adds them to the line.
+``--dump-outputs DIR`` writes what the last timed step computed (see ``dump_outputs``).
 
 ``--gpus N`` without a torchrun environment (no WORLD_SIZE) starts the N rank processes itself
 (torchrun's env: RANK, LOCAL_RANK, WORLD_SIZE, MASTER_ADDR=127.0.0.1, MASTER_PORT) before this
@@ -959,6 +966,41 @@ def table_adam_roofline(acct, D):
     return out
 
 
+DUMP_ROWS = 8192   # rows per table in --dump-outputs' sample (4 tables x 8192 x 64 fp32 = 8 MB)
+
+
+def dump_outputs(directory, step, model, w, sharded):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (float32).
+    The single-GPU step returns its workspace and updates the model in place: ``prob`` [N] and
+    ``loss`` [1] of that step, ``dense_params`` (the engine's flat buffer of every dense
+    parameter, after the step's Adam), and per table ``<table>_rows`` [DUMP_ROWS, D]: a fixed
+    seeded sample of rows after ``step.sync()`` (the deferred schedule brought current: the
+    dense-exact values), with the sampled ids in ``user_row_ids`` / ``item_row_ids`` (exact in
+    float64).  The row-sharded step: rank 0's ``loss``."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+
+    def save(name, t, dtype=torch.float32):
+        np.save(os.path.join(directory, name + ".npy"),
+                t.detach().to(device="cpu", dtype=dtype).contiguous().numpy())
+    if sharded:
+        save("loss", step.ops.last_loss.reshape(-1))
+        return
+    save("prob", w.prob.reshape(-1))
+    save("loss", w.loss.reshape(-1))
+    step.sync()
+    torch.cuda.synchronize()
+    save("dense_params", model.engine.flat)
+    g = torch.Generator().manual_seed(2024)
+    ids = {}
+    for kind, rows in (("user", model.num_users), ("item", model.num_products)):
+        ids[kind] = torch.randperm(rows, generator=g)[:DUMP_ROWS].sort().values
+        save(kind + "_row_ids", ids[kind], torch.float64)
+    for key, p in step.tables.items():      # mf_user, mf_item, mlp_user, mlp_item
+        idx = ids[key.split("_")[1]].to(p.device)
+        save(key + "_rows", p.detach()[idx])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -970,6 +1012,16 @@ def main():
     ap.add_argument("--prime", type=int, default=-1,
                     help="untimed priming steps before the warm-up of every training leg "
                          "(default 2 x sweep_every = 256: deferred-Adam steady state)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run every other section (the 8-batch "
+                         "cycle, per-kernel rooflines, inference, the drop-in / bf16 / B=256 / C1 / "
+                         "C4 lines, C5 scoring, the CPU baselines; each --no-* skips one) and print "
+                         "them in the result line; without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed as "
+                         "DIR/<name>.npy (float32): prob and loss of that step, the dense "
+                         "parameters after it, and a fixed seeded sample of rows of the four "
+                         "tables brought current; same arguments, same inputs from run to run")
     ap.add_argument("--dry-launch", action="store_true",
                     help="test the --gpus N launcher: ranks join a gloo group and report (no GPU)")
     ap.add_argument("--users", type=int, default=1_000_000)
@@ -1043,7 +1095,7 @@ def main():
         model, step = make_sharded_step(factory, U, I, lr=1e-3, weight_decay=1e-5)
     else:
         model = ncf.AdvancedNCF(U, I, 10, 50, D, D, T, hid, H, 0.2, M - 1)
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and args.full and not args.no_cpu_baseline:
             init_sd = {k: v.clone() for k, v in model.state_dict().items()}
         model = model.to(dev).train()
         step = FusedTrainStep(model, lr=1e-3, weight_decay=1e-5, graph=args.graph,
@@ -1057,13 +1109,16 @@ def main():
 
     def run_steps(fn, first, count):
         """count steps over the resident batches from index `first`; the row-sharded step plans
-        the following batch under each step (pipelined input distribution)."""
+        the following batch under each step (pipelined input distribution).  Returns what the
+        last step returned."""
+        out = None
         for s in range(first, first + count):
             u, i, t = batches[s % len(batches)]
             if sharded or (pipelined and fn is step):
-                fn(u, i, t, next=batches[(s + 1) % len(batches)][:2])
+                out = fn(u, i, t, next=batches[(s + 1) % len(batches)][:2])
             else:
-                fn(u, i, t)
+                out = fn(u, i, t)
+        return out
 
     # --- priming (deferred-Adam steady state) + warm-up
     run_steps(step, 0, prime + args.warmup)
@@ -1072,7 +1127,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(step, prime + args.warmup, args.steps)
+    last_w = run_steps(step, prime + args.warmup, args.steps)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -1082,6 +1137,46 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     ms_step = elapsed / args.steps * 1e3
+    dfr = step.deferred if hasattr(step, "deferred") else getattr(
+        getattr(step, "ops", None), "deferred", None)
+    head = {
+        "metric": METRIC,
+        "value": round(N * world * args.steps / elapsed, 1),
+        "unit": "samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic: users uniform, positive items Zipf(1.05), 4 uniform negatives; random-init weights",
+        "config": {"workload": "C2 train step: 1M users x 100K items, D=64, H=4, MLP [256,128,64], "
+                               "T=32, dropout 0.2, Adam lr 1e-3 wd 1e-5 (dense-exact)",
+                   "global_batch": N * world, "groups_per_gpu": B, "samples_per_group": M,
+                   "launch": ("host launches (row-sharded step)" if sharded else
+                              "hipGraph replay of the captured step" if args.graph else
+                              "host launches"),
+                   "parallelism": (f"dp{world} + row-sharded tables (RCCL all-to-all), "
+                                   "dense all-reduce") if sharded else "single-gpu",
+                   **({"exchange": type(step.x).__name__} if sharded else {})},
+        "adam_steady_state": steady_state(prime, args.warmup,
+                                          int(dfr.sweep_every) if dfr is not None else None),
+        "prime_steps": prime,
+        "resident_batches": args.batches,
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, model, last_w, sharded)
+    if not args.full:
+        # the plain run: the headline alone
+        if rank == 0:
+            last = step.ops.last_loss if sharded else step.last_loss
+            head["final_loss"] = round(float(last.item()) if last is not None else float("nan"), 6)
+            print(json.dumps(head), flush=True)
+        if sharded:
+            dist.destroy_process_group()
+        return
     # the same timed region cycling over 8 of the resident batches (the round-3 headline's
     # reuse cycle, whose rows and Adam state fit the 256 MB Infinity Cache), reported beside
     # the headline once
@@ -1349,27 +1444,7 @@ def main():
 
     if rank == 0:
         rec = {
-            "metric": METRIC,
-            "value": round(samples_s, 1),
-            "unit": "samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic: users uniform, positive items Zipf(1.05), 4 uniform negatives; random-init weights",
-            "config": {"workload": "C2 train step: 1M users x 100K items, D=64, H=4, MLP [256,128,64], "
-                                   "T=32, dropout 0.2, Adam lr 1e-3 wd 1e-5 (dense-exact)",
-                       "global_batch": N * world, "groups_per_gpu": B, "samples_per_group": M,
-                       "launch": ("host launches (row-sharded step)" if sharded else
-                                  "hipGraph replay of the captured step" if args.graph else
-                                  "host launches"),
-                       "parallelism": (f"dp{world} + row-sharded tables (RCCL all-to-all), "
-                                       "dense all-reduce") if sharded else "single-gpu",
-                       **({"exchange": type(step.x).__name__} if sharded else {})},
+            **head,
             "roofline": {"bound": "mfma", "kernel": KERNEL_SYMBOL.get(dom, dom),
                          "entry_point": dom,
                          "achieved": round(dom_tf, 2), "peak": FP32_MFMA_PEAK_TFS, "unit": "TFLOP/s",

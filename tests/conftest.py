@@ -15,8 +15,18 @@ def pytest_configure(config):
 
 
 def load_npz(name):
-    with np.load(os.path.join(GOLDEN, name), allow_pickle=False) as z:
-        return {k: z[k] for k in z.files}
+    """A fixture's arrays; one split into ``<stem>.partNN.npz`` files (make_goldens.py
+    savez_parts: committed files stay below 1 MiB) is joined, keys in order."""
+    files = [name]
+    if not os.path.exists(os.path.join(GOLDEN, name)):
+        stem = name[:-len(".npz")] + ".part"
+        files = sorted(f for f in os.listdir(GOLDEN) if f.startswith(stem) and f.endswith(".npz"))
+        assert files, f"no fixture {name}"
+    out = {}
+    for f in files:
+        with np.load(os.path.join(GOLDEN, f), allow_pickle=False) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def sub(d, prefix):

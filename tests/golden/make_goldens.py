@@ -23,7 +23,8 @@ Fixtures written to tests/golden/*.npz (inputs and expected outputs only):
   F1 f1_eval_demo.npz      eval forward known-answer: 1000 pairs of the reference's
                            src/inference/demo/data/predictions.csv, the checkpoint rows
                            they touch (ids remapped to 0..n-1), reference re-run outputs
-  F2 f2_train_c2.npz       train goldens, C2 architecture at small scale, dropout=0
+  F2 f2_train_c2.part*.npz train goldens, C2 architecture at small scale, dropout=0 (split
+                           into parts below 1 MiB each; conftest.load_npz joins them)
   F3 f3_train_c1.npz       train goldens, C1 architecture (D=16, H=1, MLP [64,32])
   F4 f4_ops.npz            MultiHeadAttention (L=5 and L=50) and TemporalEncoding fwd+bwd
   F5 f5_scoring.npz        forward_simple(hour=None) 8 users x 366 items + top-10,
@@ -131,6 +132,30 @@ def make_f1(ref, AdvancedNCF, KJT, sd):
 
 # ----------------------------------------------------------------------------- F2/F3
 ZONE = 1e-6   # = tests/parity.py ZONE
+PART_BYTES = 700 * 1024   # raw array bytes per file of a split fixture (committed files < 1 MiB)
+
+
+def savez_parts(fname, out):
+    """One ``fname`` when the arrays fit PART_BYTES, else ``<stem>.part00.npz``, ``.part01.npz``,
+    ...: the keys in order, a new part whenever the next array would pass PART_BYTES
+    (tests/conftest.py load_npz reads the parts back into one dict, keys in the same order)."""
+    stem = fname[:-len(".npz")]
+    parts, size = [{}], 0
+    for k, v in out.items():
+        n = np.asarray(v).nbytes
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    for old in os.listdir(HERE):      # an earlier layout of the same fixture
+        if old == fname or (old.startswith(stem + ".part") and old.endswith(".npz")):
+            os.remove(os.path.join(HERE, old))
+    if len(parts) == 1:
+        np.savez_compressed(os.path.join(HERE, fname), **out)
+        return
+    for j, p in enumerate(parts):
+        np.savez_compressed(os.path.join(HERE, f"{stem}.part{j:02d}.npz"), **p)
 
 
 def make_batch(g, U, I, B, M):
@@ -205,7 +230,7 @@ def make_train(fname, AdvancedNCF, KJT, U, I, D, T, hidden, H, B, M, steps, seed
     out["cfg"] = np.array([U, I, D, T, H, B, M, steps], np.int64)
     out["hidden"] = np.array(hidden, np.int64)
     out["hparams"] = np.array([lr, wd], np.float64)
-    np.savez_compressed(os.path.join(HERE, fname), **out)
+    savez_parts(fname, out)
     print(f"{fname}: losses", [float(out[f'step{s}/loss']) for s in range(steps)])
 
 
@@ -388,6 +413,31 @@ def make_f9(ref):
     print("F9 written;", len(meta), "cases")
 
 
+def make_demo_dir(ref, limit=64 * 1024):
+    """demo_model_dir/: the reference's unzipped demo checkpoint directory itself (data.pkl,
+    version, byteorder, .data/serialization_id, data/<key>) without the storages above ``limit``
+    bytes; omitted.json lists those (name -> bytes) so a test can zero-fill them
+    (tests/test_cpu_host.py test_load_reference_demo_directory reads keys, order and shapes)."""
+    import json
+    import shutil
+    src, dst = os.path.join(ref, DEMO), os.path.join(HERE, "demo_model_dir")
+    shutil.rmtree(dst, ignore_errors=True)
+    omitted = {}
+    for root, _, files in os.walk(src):
+        for f in sorted(files):
+            p = os.path.join(root, f)
+            rel = os.path.relpath(p, src)
+            if os.path.getsize(p) > limit:
+                omitted[os.path.basename(p)] = os.path.getsize(p)
+                continue
+            os.makedirs(os.path.dirname(os.path.join(dst, rel)), exist_ok=True)
+            shutil.copyfile(p, os.path.join(dst, rel))
+    with open(os.path.join(dst, "omitted.json"), "w") as fh:
+        json.dump(dict(sorted(omitted.items(), key=lambda kv: int(kv[0]))), fh, indent=1)
+        fh.write("\n")
+    print("demo_model_dir written;", len(omitted), "storages omitted")
+
+
 def make_train_fixtures(AdvancedNCF, KJT):
     make_train("f2_train_c2.npz", AdvancedNCF, KJT, U=300, I=120, D=64, T=32,
                hidden=[256, 128, 64], H=4, B=8, M=5, steps=3, seed=0, lr=1e-3, wd=1e-5)
@@ -420,6 +470,7 @@ def main():
     make_f7(a.reference)
     make_f8(a.reference)
     make_f9(a.reference)
+    make_demo_dir(a.reference)
 
 
 if __name__ == "__main__":

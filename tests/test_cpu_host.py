@@ -285,13 +285,22 @@ def test_load_unzipped_archive_roundtrip(tmp_path):
         assert torch.equal(got[k], sd[k]) and got[k].stride() == sd[k].stride()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/inference/demo/train_20241225_002713_model"),
-                    reason="reference checkout not present")
-def test_load_reference_demo_directory():
+def test_load_reference_demo_directory(tmp_path):
     """The reference's own unzipped demo checkpoint (consolidate_shards.py's input) loads with
-    all 62 keys in order and the AdvancedNCF shapes (safe loader; container-only check)."""
+    all 62 keys in order and the AdvancedNCF shapes (safe loader).  tests/golden/demo_model_dir
+    is that directory (its data.pkl, version, byteorder, serialization id and every storage up
+    to 64 KiB); the seven larger storages (omitted.json: name -> bytes) are zero-filled here."""
+    import json
+    import shutil
     from ncf_amd.checkpoint import load_unzipped_archive
-    sd = load_unzipped_archive("/root/reference/src/inference/demo/train_20241225_002713_model")
+    model_dir = tmp_path / "train_20241225_002713_model"
+    shutil.copytree(os.path.join(ROOT, "tests", "golden", "demo_model_dir"), model_dir)
+    with open(model_dir / "omitted.json") as f:
+        omitted = json.load(f)
+    os.remove(model_dir / "omitted.json")
+    for name, nbytes in omitted.items():
+        (model_dir / "data" / name).write_bytes(bytes(nbytes))
+    sd = load_unzipped_archive(str(model_dir))
     assert len(sd) == 62 and list(sd)[0] == "mf_norm.weight"
     assert sd["mf_embedding_collection.embedding_bags.user_id.weight"].shape == (8031, 64)
     assert sd["mlp.0.weight"].shape == (256, 96)

@@ -1,7 +1,8 @@
 """bench.py with ncf_amd module constants overridden first (A/B of a constant on any bench leg,
 torchrun included):
-    python tools/bench_set.py --set distributed.SWEEP_EVERY=128 -- --sharded --steps 200
-    python -m torch.distributed.run --nproc-per-node 1 ... tools/bench_set.py --set ... -- --sharded"""
+    python tools/bench_set.py --set distributed.SWEEP_EVERY=128 -- --full --sharded --steps 200
+    python -m torch.distributed.run --nproc-per-node 1 ... tools/bench_set.py --set ... -- --full --sharded
+(``--full``: the sections after the headline, bench.py's own option)"""
 import importlib
 import os
 import sys

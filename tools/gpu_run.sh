@@ -4,9 +4,9 @@
 #   tests            the whole -m gpu suite
 #   fullsize         tests/test_gpu_fullsize.py only
 #   t:<pytest -k>    the -m gpu tests matching the expression
-#   bench            python bench.py (defaults), JSON line -> gpurun_out/TAG_bench.json
-#   quick            bench.py --steps 100 --warmup 10 --no-c4 --no-score
-#   sharded          bench.py --sharded (the row-sharded step at world 1) -> TAG_sharded.json
+#   bench            python bench.py --full (defaults: every section), JSON line -> TAG_bench.json
+#   quick            bench.py --full --steps 100 --warmup 10 --no-c4 --no-score
+#   sharded          bench.py --full --sharded (the row-sharded step at world 1) -> TAG_sharded.json
 #   dropinhost       tools/dropin_host.py (host time of the reference call pattern, cProfile)
 #   prof             rocprofv3 --kernel-trace --stats over a short bench (C2 legs only)
 #   pmc              FETCH_SIZE / WRITE_SIZE passes over the same command (tools/pmc_run.sh;
@@ -38,7 +38,7 @@ tree = [subprocess.run(["python3", "neural-collaborative-filtering-demo_amd/_abi
 print("library:", lib.ncf_build_info().decode(), "| tree: abi=%s src=%s" % tuple(tree))
 PYEOF
 PYT="python -u -m pytest -x -q --timeout 300 --timeout-method thread -p no:cacheprovider"
-QUICK="bench.py --steps 60 --warmup 10 --prime 128 --no-c4 --no-score --no-cpu-baseline --no-dropin --no-extra"
+QUICK="bench.py --full --steps 60 --warmup 10 --prime 128 --no-c4 --no-score --no-cpu-baseline --no-dropin --no-extra"
 for what in "$@"; do
   echo "== $TAG $what $(date +%T)"
   case "$what" in
@@ -52,17 +52,17 @@ for what in "$@"; do
       timeout -k 10 600 $PYT -v tests -m gpu -k "${what#t:}" > "$OUT/${TAG}_t.log" 2>&1
       rc=$? ;;
     bench)
-      timeout -k 10 900 python -u bench.py > "$OUT/${TAG}_bench.log" 2>&1
+      timeout -k 10 900 python -u bench.py --full > "$OUT/${TAG}_bench.log" 2>&1
       rc=$?
       grep '^{' "$OUT/${TAG}_bench.log" | tail -1 > "$OUT/${TAG}_bench.json" ;;
     quick)
-      timeout -k 10 300 python -u bench.py --steps 100 --warmup 10 --no-c4 --no-score --no-extra \
+      timeout -k 10 300 python -u bench.py --full --steps 100 --warmup 10 --no-c4 --no-score --no-extra \
         > "$OUT/${TAG}_quick.log" 2>&1
       rc=$?
       grep '^{' "$OUT/${TAG}_quick.log" | tail -1 > "$OUT/${TAG}_quick.json" ;;
     sharded)
       timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-        --master-addr 127.0.0.1 --master-port 29517 bench.py --sharded --steps 200 --warmup 20 \
+        --master-addr 127.0.0.1 --master-port 29517 bench.py --full --sharded --steps 200 --warmup 20 \
         --no-c4 --no-score --no-cpu-baseline --no-dropin > "$OUT/${TAG}_sharded.log" 2>&1
       rc=$?
       grep '^{' "$OUT/${TAG}_sharded.log" | tail -1 > "$OUT/${TAG}_sharded.json" ;;
@@ -75,7 +75,7 @@ for what in "$@"; do
         python3 $QUICK > "$OUT/${TAG}_prof.log" 2>&1
       rc=$? ;;
     pmc)
-      PMC_CMD="python3 $QUICK" timeout -k 10 700 bash tools/pmc_run.sh "$TAG" \
+      PMC_OUT="$OUT" PMC_CMD="python3 $QUICK" timeout -k 10 700 bash tools/pmc_run.sh "$TAG" \
         > "$OUT/${TAG}_pmc.log" 2>&1
       rc=$?
       cp "profiles/${TAG}_pmc_traffic.json" "$OUT/" 2>/dev/null ;;
@@ -85,7 +85,7 @@ for what in "$@"; do
         python3 tools/dropin_host.py --warmup 150 --steps 60 > "$OUT/${TAG}_dropinprof.log" 2>&1
       rc=$? ;;
     c5pmc)
-      PMC_CMD="python3 tools/score_bench.py --k 10 100 --reps 1" timeout -k 10 500 \
+      PMC_OUT="$OUT" PMC_CMD="python3 tools/score_bench.py --k 10 100 --reps 1" timeout -k 10 500 \
         bash tools/pmc_run.sh "${TAG}_c5" > "$OUT/${TAG}_c5pmc.log" 2>&1
       rc=$?
       cp "profiles/${TAG}_c5_pmc_traffic.json" "$OUT/" 2>/dev/null ;;
@@ -116,7 +116,7 @@ for what in "$@"; do
         for v in "$va" "$vb"; do
           f="$OUT/${TAG}_sab_$(basename "$v")_$k.log"
           env "$var=$v" timeout -k 10 200 python3 -m torch.distributed.run --nnodes=1 \
-            --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --sharded \
+            --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --full --sharded \
             --steps 100 --warmup 20 --prime 128 --no-c4 --no-score --no-cpu-baseline --no-dropin \
             > "$f" 2>&1 || { rc=$?; break 2; }
           python3 tools/bench_summ.py "$f" "$var=$v" >> "$OUT/${TAG}_sab.log" 2>&1
@@ -131,7 +131,7 @@ for what in "$@"; do
         for where in "$d" .; do
           f="$OUT/${TAG}_dirsab_$(basename "$where")_$k.log"
           extra=""
-          [ "$where" = "." ] && extra="--batches 8"   # (the earlier bench cycled 8 batches)
+          [ "$where" = "." ] && extra="--batches 8 --full"   # (the earlier bench cycled 8 batches, all sections)
           (cd "$where" && timeout -k 10 200 python3 -m torch.distributed.run --nnodes=1 \
             --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --sharded \
             --steps 100 --warmup 20 --prime 128 --no-c4 --no-score --no-cpu-baseline \

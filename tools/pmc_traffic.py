@@ -51,7 +51,7 @@ def main():
                                        "hbm_bytes_per_launch")})
     with open(out, "w") as fh:
         json.dump({"method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes "
-                             "over `bench.py --steps 5 --warmup 3`; FETCH_SIZE x2 (gfx950), KiB x1024; "
+                             "over `bench.py --full --steps 5 --warmup 3`; FETCH_SIZE x2 (gfx950), KiB x1024; "
                              "mean per launch", "kernels": kernels}, fh, indent=1, sort_keys=True)
     for k, v in sorted(kernels.items()):
         print(f"{k:28s} grid {v['grid']:>9d}  fetch {v['fetch_bytes_per_launch'] / 1e6:9.3f} MB  "
