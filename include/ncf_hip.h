@@ -39,22 +39,14 @@ typedef struct ncf_step_clock {
   uint64_t seed;
 } ncf_step_clock;
 int ncf_step_clock_advance(ncf_step_clock* clock, uint64_t base_seed, void* stream);
-/* Sets *clock = {t, 0, seed} on `stream` (a side stream's own copy of the step clock, set from the
- * host's step counter: kernels queued there read their step targets from it while the step's
- * stream advances the live clock without waiting for them). */
-int ncf_step_clock_set(ncf_step_clock* clock, int32_t t, uint64_t seed, void* stream);
 
 /* One wavefront waiting `microseconds` (<= 1e6) of wall-clock time on `stream`: the overlap
  * probe of a step's side streams (two spins on two streams finish in about one span when the
  * streams reach the GPU through different hardware queues).                                   */
 int ncf_stream_spin(int64_t microseconds, void* stream);
-/* A stream restricted to `keep_per8` of every 8 compute units (hipExtStreamCreateWithCUMask;
- * its own hardware queue), and its destruction.  Side-stream placement knob.                   */
-int ncf_stream_create_cu_mask(int32_t keep_per8, void** out);
 /* Blocks per CU the rolling table sweep launches at most (grid-stride beyond; default 16).
  * per_cu <= 0 queries.  Returns the previous value.  (A/B: the overlapped sweep's footprint.) */
 int64_t ncf_adam_sweep_set_blocks(int64_t per_cu);
-int ncf_stream_destroy(void* stream);
 int ncf_version(void);
 const char* ncf_last_error(void);
 int ncf_device_count(void);

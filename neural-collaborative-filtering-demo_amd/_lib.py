@@ -63,8 +63,6 @@ SIGNATURES = {
     "ncf_reduce_batch_scratch": (I64, [P]),
     "ncf_reduce_set_vec": (I64, [I64]),
     "ncf_stream_spin": (I32, [I64, P]),
-    "ncf_stream_create_cu_mask": (I32, [I32, P]),
-    "ncf_stream_destroy": (I32, [P]),
     "ncf_adam_sweep_set_blocks": (I64, [I64]),
     "ncf_dropout_rows": (I32, [P, I64, I64, I64, F32, U64, P, P, P]),
     "ncf_reduce_batch": (I32, [P, P, I64, P]),
@@ -158,7 +156,6 @@ SIGNATURES = {
                                   F64, F64, P]),
     "ncf_adam_sweep": (I32, [P, P, P, P, P, P, I64, I64, I64, P, I32, P, F64, F64, F64, F64, P]),
     "ncf_step_clock_advance": (I32, [P, U64, P]),
-    "ncf_step_clock_set": (I32, [P, I32, U64, P]),
     "ncf_adam_rows_catchup_clock": (I32, [P, P, P, P, P, P, I64, P, P, I32, I64, P, I32, P, P, F64,
                                           F64, F64, F64, P]),
     "ncf_adam_rows_apply_clock": (I32, [P, P, P, P, P, P, P, P, I64, P, P, I32, I64, P, I32, P, P,
@@ -552,21 +549,6 @@ def streams_overlap(side, main, us: int = 400) -> bool:
 
 # Side streams tried before giving up on one that runs beside the step's stream
 SIDE_STREAM_TRIES = 8
-
-
-_MASKED = []     # CU-masked streams made here (alive for the process)
-
-
-def masked_stream(device, keep_per8: int):
-    """A torch stream (ExternalStream) whose kernels use `keep_per8` of every 8 CUs."""
-    out = ctypes.c_void_p()
-    lib = _lib if _lib is not None else load()
-    with torch.cuda.device(device):
-        check(lib.ncf_stream_create_cu_mask(int(keep_per8), ctypes.byref(out)),
-              "ncf_stream_create_cu_mask")
-    s = torch.cuda.ExternalStream(out.value, device=device)
-    _MASKED.append(s)
-    return s
 
 
 def side_stream(device, priority: int = 0, main=None):

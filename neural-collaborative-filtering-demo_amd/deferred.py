@@ -67,9 +67,6 @@ LATE_CATCHUP = True
 # HIP stream priority of the overlapped sweep's side stream (torch.cuda.Stream priority: 0 the
 # default, -1 high)
 SIDE_PRIORITY = 0
-# The side stream's kernels on `SIDE_CU_KEEP` of every 8 CUs (a CU-masked stream, its own
-# hardware queue); 0: a pool stream on every CU (the default, _lib.side_stream)
-SIDE_CU_KEEP = 0
 # The overlapped rolling sweep (below) for FusedTrainStep and the optimizer hook: on (False: the
 # sweep on the step's own stream)
 OVERLAP_SWEEP = True
@@ -157,13 +154,6 @@ class DeferredTableAdam:
         self._side = None
         self._ev = None
         self._joined = True
-        # a late catch-up left running past its step (trainer.LATE_DETACHED): the event the next
-        # user of the tables waits for (late_join), and the clock copy it reads its target from
-        self._late_ev = None
-        self._late_clock = None
-        self._side_t = None        # the t the side clock was last set to (side_clock)
-        self._side_ordered_t = -1  # the side stream is ordered after the table apply closing t + 1
-        self._live_pending = False  # a sweep part reading the live clock awaits the step's join
         engine.deferred = self
         if self.overlap and not torch.cuda.is_current_stream_capturing():
             self.side_stream()     # (picked and checked here, outside any stream capture)
@@ -324,14 +314,13 @@ class DeferredTableAdam:
                 r0 = k * sl
                 self._sweep_range(kind, r0, max(0, min(rows, r0 + sl) - r0), st)
 
-    def _rolling(self, st, step_rel, part=0, nparts=1, clock=None):
+    def _rolling(self, st, step_rel, part=0, nparts=1):
         """Rolling sweep closing step clock->t + step_rel (slice of that step; part `part` of
-        `nparts` consecutive row ranges of it); ``clock``: a side clock (side_clock) instead of
-        the live one."""
+        `nparts` consecutive row ranges of it)."""
         pairs = self.__dict__.get("_sweep_pairs") or self.__dict__.setdefault("_sweep_pairs",
                                                                                self._pairs())
         D = self.engine.model.mlp_embedding_dim
-        clk = ptr(self.clock if clock is None else clock)
+        clk = ptr(self.clock)
         if nparts == 1:
             _lib.call("ncf_adam_pairs_sweep_rolling", ctypes.addressof(pairs), 2, D,
                       self.sweep_every, step_rel, clk, ptr(self._table), *self._consts(), st)
@@ -360,7 +349,6 @@ class DeferredTableAdam:
         self._ev[1].record(side)
         self._owed.remove(part)
         self._joined = False
-        self._live_pending = True      # (it reads the live clock: joined before the advance)
 
     def fork_part(self, at):
         """The part of the owed sweep forked at engine fork point `at`, or None: fork_points,
@@ -374,8 +362,7 @@ class DeferredTableAdam:
     def side_stream(self):
         """The overlapped sweep's stream (created on first use)."""
         if self._side is None:     # (one that runs beside the step's stream: _lib.side_stream)
-            self._side = (_lib.masked_stream(self.clock.device, SIDE_CU_KEEP) if SIDE_CU_KEEP
-                          else _lib.side_stream(self.clock.device, SIDE_PRIORITY))
+            self._side = _lib.side_stream(self.clock.device, SIDE_PRIORITY)
             self._ev = (_lib.RawEvent(stream_only=True), _lib.RawEvent(stream_only=True))
         return self._side
 
@@ -384,61 +371,12 @@ class DeferredTableAdam:
         it) is what the step's sweep join waits for."""
         self._ev[1].record(stream)
 
-    def late_join(self, st=None):
-        """Stream st (default: the current stream) waits for a late catch-up that was left
-        running past the step that queued it (trainer.LATE_DETACHED): before anything on st
-        reads or steps table rows again (the next prepare, a flush, a sync)."""
-        ev, self._late_ev = self._late_ev, None
-        if ev is not None:
-            ev.wait(st if st is not None else _lib.stream_ptr(self.clock.device))
-
     def sweep_join(self):
         """The current stream waits for the side-stream sweep (before the step's apply and the
         clock advance that would change the sweep's target under it)."""
         if not self._joined:
             self._ev[1].wait(_lib.stream_ptr(self.clock.device))
             self._joined = True
-            self._live_pending = False
-
-    # ---- trainer.SIDE_AHEAD: the side stream's work off the step's queue
-    def side_clock(self, st):
-        """The side stream's own step clock, t = the host's step counter, set on stream st (the
-        side stream) when that changed: the late catch-up and the sweep queued there read their
-        targets from it, so the step's stream advances the live clock without joining them."""
-        if self._late_clock is None:
-            # (no fill: written by ncf_step_clock_set on the side stream before any reader)
-            self._late_clock = torch.empty_like(self.clock)
-        if self._side_t != self.t:
-            _lib.call("ncf_step_clock_set", ptr(self._late_clock), self.t, 0, st)
-            self._side_t = self.t
-        return self._late_clock
-
-    def side_ordered(self):
-        """The side stream has waited for the table apply closing step t + 1 (the trainer's
-        tables-done event): after this step's advance, its owed sweep may run there."""
-        self._side_ordered_t = self.t
-
-    def sweep_owed(self, side):
-        """Every owed part of the closed step's rolling sweep on stream `side` now, its target
-        (t) from the side clock, when that stream is ordered after the closed step's table
-        apply (side_ordered; else the parts stay owed for the engine's fork points).  The
-        batch rows of that step carry its stamp and are skipped, the next batch's rows were
-        caught up ahead of it on the same stream (the late catch-up), every other row is the
-        sweep's alone; a catch-up on the step's stream first joins it (prepare)."""
-        if not self._owed or self._side_ordered_t != self.t - 1:
-            return False
-        clk = self.side_clock(side)
-        n = len(self.fork_points)
-        for part in sorted(self._owed):
-            if _lib.PROFILE is not None:   # (per-launch instrumentation times it on its stream)
-                with torch.cuda.stream(self._side):
-                    self._rolling(side, 0, part, n, clock=clk)
-            else:
-                self._rolling(side, 0, part, n, clock=clk)
-        self._owed = []
-        self._ev[1].record(side)
-        self._joined = False
-        return True
 
     def _settle(self, st):
         """Parts of the owed sweep whose fork point this step did not pass: on stream st, now
@@ -450,7 +388,6 @@ class DeferredTableAdam:
     def flush(self, st):
         """Settle any owed / in-flight sweep on the current stream (before full sweeps or
         anything that reads the tables from the host side)."""
-        self.late_join(st)
         self.sweep_join()
         self._settle(st)
 
@@ -474,7 +411,6 @@ class DeferredTableAdam:
         m = eng.model
         n = w.g.n
         self._rows_now = n
-        self.late_join(st)
         if (CLAIM_CATCHUP and self.clock is not None and n > 0 and not getattr(w, "prededuped", None)
                 and not torch.cuda.is_current_stream_capturing()):
             self._prepare_claim(w, uid, iid, st)
@@ -494,7 +430,8 @@ class DeferredTableAdam:
                 self._locked = False
                 self.late_skips += 1
                 return
-            # (a sweep still running on the side stream may hold rows of this batch: SIDE_AHEAD)
+            # (a sweep forked by a training forward whose step was never closed — no apply —
+            # still runs on the side stream and may hold rows of this batch)
             self.sweep_join()
             pairs = self._pairs_for(w)
             # (locked: an early catch-up of the next batch may run during this step)
@@ -517,7 +454,7 @@ class DeferredTableAdam:
         m = self.engine.model
         n = w.g.n
         self._ensure(self.t + 1)
-        self.sweep_join()             # (a side sweep left running past its step: SIDE_AHEAD)
+        self.sweep_join()             # (a sweep forked by a forward whose step never closed)
         pairs = self._pairs_for(w)
         self._locked = False          # (no early catch-up during a claim-path step)
         _lib.call("ncf_adam_pairs_catchup_claim_clock", ctypes.addressof(pairs), 2,
@@ -564,18 +501,18 @@ class DeferredTableAdam:
         self._catchup_next(rows, n, stream)
         return True
 
-    def late_catchup(self, rows, n, stream, clock=None):
+    def late_catchup(self, rows, n, stream):
         """The next batch's unique rows (a dedup set, as early_catchup) caught up through the
         step now running, on `stream`, which must be ordered after this step's table apply (the
         apply fused into the embedding backward) and its sweep; the set is marked, so the next
         step's prepare skips its catch-up.  The caller joins `stream` before the clock advance."""
         if self.clock is None or n <= 0:
             return False
-        self._catchup_next(rows, n, stream, clock)
+        self._catchup_next(rows, n, stream)
         rows["late_t"] = self.t + 1
         return True
 
-    def _catchup_next(self, rows, n, stream, clock=None):
+    def _catchup_next(self, rows, n, stream):
         self._ensure(self.t + 2)
         cache = self.__dict__.setdefault("_early_pairs", {})
         key = (getattr(self, "_gen", 0), rows["uniq_u"].data_ptr(), rows["uniq_i"].data_ptr())
@@ -588,8 +525,7 @@ class DeferredTableAdam:
                 pairs[k].row_ids = ptr(ids)
         _lib.call("ncf_adam_pairs_catchup_lock_clock", ctypes.addressof(pairs), 2,
                   self.engine.model.mlp_embedding_dim, ptr(rows["num_unique"]), n, 1, 0,
-                  ptr(self.clock if clock is None else clock), ptr(self._table), *self._consts(),
-                  stream)
+                  ptr(self.clock), ptr(self._table), *self._consts(), stream)
 
     def fused_apply_args(self, w):
         """The arguments of the apply fused into the embedding backward (engine.backward
@@ -604,16 +540,12 @@ class DeferredTableAdam:
         return (ctypes.addressof(pairs), ptr(self.clock), ptr(self._table)) + self._consts()
 
     # ---- after the backward: this step's gradient on the touched rows
-    def apply(self, w, st, late_join: bool = False):
-        """``late_join`` (the step's table apply already ran inside the embedding backward): the
-        side stream is not joined here; the caller joins it (sweep_join) before the clock
-        advance.  Only when no sweep part is owed (those run on st and must follow the join)."""
+    def apply(self, w, st):
         n = w.g.n
         if self.clock is not None:
             self._ensure(self.t + 1)
-            if not (late_join and getattr(w, "applied", False) and not self._owed):
-                self.sweep_join()
-                self._settle(st)
+            self.sweep_join()
+            self._settle(st)
             if n > 0 and not getattr(w, "applied", False):
                 pairs = self._pairs_for(w)
                 _lib.call("ncf_adam_pairs_apply_clock", ctypes.addressof(pairs), 2,
@@ -660,8 +592,6 @@ class DeferredTableAdam:
 
     def sync(self):
         """Catch every row up to the current step (tables + moments become the dense values)."""
-        if self.clock is not None:
-            self.late_join()
         if self.t == 0 or self.synced_t == self.t:
             return
         self._sweep(_lib.stream_ptr(self.tables["mf_user"].device))

@@ -46,7 +46,7 @@ from ._lib import ptr
 # launch-tape slots of the row-sharded step (tapes.py): pointer ranges first (the next batch's
 # ids, the targets, the compute stream), then the per-step scalars
 SLOT_NEXT_U, SLOT_NEXT_I, SLOT_TARGETS, SLOT_STREAM = 0, 1, 2, 3
-SLOT_TOKEN, SLOT_NMAX, SLOT_NUNI, SLOT_TOKEN_NEXT = 4, 5, 6, 7
+SLOT_TOKEN, SLOT_NMAX, SLOT_NUNI = 4, 5, 6
 TAPE_SHARDED = True
 # The next step's rows sent to their owners during this step (on the side communicator)
 SHARD_AHEAD = True
@@ -70,13 +70,6 @@ GRAD_ROWS = True
 # batch row at its send position; ncf_gather_ln_gmf_ld_fwd, table_ld = 2 D) instead of copying
 # them into compact mini tables first (ncf_shard_rows); needs GRAD_ROWS
 BACK_ROWS = True
-# The owner's claim of the next step's rows (dedup + positions, ncf_shard_owner_prepare) run a
-# step ahead on the plan stream, right behind the exchange that sends them (ahead mode); the step
-# itself then only catches those rows up.  Same bits (tools/shard_bisect.py).  Off: measured at
-# world 1 (2 interleaved runs each) 0.3292 / 0.3638 ms/step against 0.3305 / 0.3282 without —
-# the claim leaves the critical path (17.7 -> 5.7 us) but the plan stream's extra work beside
-# the fused backward slows it by as much (110 -> 122 us)
-CLAIM_AHEAD = False
 
 
 class ShardExchange:
@@ -360,24 +353,6 @@ class ShardedTrainStep:
         self.x.counts_issue(p)
         return p
 
-    def _claims_ahead(self):
-        return CLAIM_AHEAD and hasattr(self.ops, "owner_claim")
-
-    def _claim_ahead(self, nxt, ahead, token_slot=SLOT_TOKEN):
-        """Step t+1's owner claim (dedup + positions of the rows it was just sent) on the plan
-        stream behind their exchange; the ahead event is recorded again behind it, so the step
-        that uses it waits for both.  Returns its owner state (owner_host)."""
-        ops = self.ops
-        own = ops.owner_host(nxt)
-        ps = nxt.stream
-        ops.owner_claim(ahead[0], own, ps.cuda_stream, token_slot)
-        ev = ahead[1]
-        if isinstance(ev, _lib.RawEvent):
-            ev.record(ps.cuda_stream)
-        elif ev is not None:
-            ev.record(ps)
-        return own
-
     def _settle_pending(self, pend):
         """A pending next-step plan that is not used (other ids came): its launches on the plan
         stream must be behind the step before the buffers of its set are written again."""
@@ -390,16 +365,15 @@ class ShardedTrainStep:
         ops, X = self.ops, self.x
         ops.mark_entry()          # ids of this call and of `next` exist from here on
         pend, self._pending = self._pending, None
-        ahead = own = None
+        ahead = None
         if pend is not None and pend[0] is user_ids and pend[1] is item_ids:
             plan, ahead = pend[2], pend[3]   # planned (and its rows sent) one call ago
-            own = pend[4]                    # (and claimed by their owners, CLAIM_AHEAD)
         else:
             self._settle_pending(pend)
             plan = self.plan(user_ids, item_ids)
         X.counts_wait(plan)
         if next is not None:      # plan step t+1 now: it runs under this step's GPU work
-            self._pending = [next[0], next[1], self.plan(next[0], next[1]), None, None]
+            self._pending = [next[0], next[1], self.plan(next[0], next[1]), None]
         ops.begin(plan)
         send_splits, recv_splits = plan.splits()
         if ahead is not None:
@@ -407,10 +381,7 @@ class ShardedTrainStep:
             X.wait_ahead(*ahead)
         else:
             recv = X.exchange(plan.send, send_splits, recv_splits)
-        if own is not None:       # claimed a step ahead: its rows only need catching up
-            ops.owner_catchup(own)
-        else:
-            own = ops.owner_prepare(recv, plan)
+        own = ops.owner_prepare(recv, plan)
         rows = ops.owner_gather(own, recv)
         back = X.exchange(rows, recv_splits, send_splits, slot="rows")
         grads, loss = ops.compute(plan, back, user_ids, item_ids, targets,
@@ -419,8 +390,6 @@ class ShardedTrainStep:
             nxt = self._pending[2]
             X.counts_wait(nxt)
             self._pending[3] = X.exchange_ahead(nxt)
-            if self._claims_ahead():
-                self._pending[4] = self._claim_ahead(nxt, self._pending[3])
         ar = X.all_reduce_start(ops.dense_grad())
         got = X.exchange(grads, send_splits, recv_splits, slot="grads")
         ops.owner_apply(own, got)
@@ -447,9 +416,9 @@ class ShardedTrainStep:
         ops.eng.ensure_layout()   # (as eng.forward would; a re-pack moves the signature)
         ops.mark_entry()
         pend, self._pending = self._pending, None
-        ahead = own_ahead = None
+        ahead = None
         if pend is not None and pend[0] is user_ids and pend[1] is item_ids:
-            plan, ahead, own_ahead = pend[2], pend[3], pend[4]
+            plan, ahead = pend[2], pend[3]
         else:
             self._settle_pending(pend)
             plan = self.plan(user_ids, item_ids)
@@ -459,10 +428,10 @@ class ShardedTrainStep:
         if next is not None:
             nu_, ni_ = next[0].reshape(-1), next[1].reshape(-1)
             nplan = ops.plan_host(nu_, ni_)
-            self._pending = [next[0], next[1], nplan, None, None]
+            self._pending = [next[0], next[1], nplan, None]
         targets = targets.reshape(-1).to(device=ops.dev, dtype=torch.float32).contiguous()
         send_splits, recv_splits = plan.splits()
-        own = own_ahead if own_ahead is not None else ops.owner_host(plan)
+        own = ops.owner_host(plan)
         nu, ni = plan.totals()
         X.site("recv", send_splits, recv_splits)
         X.site("rows", recv_splits, send_splits)
@@ -470,7 +439,7 @@ class ShardedTrainStep:
         T.horizon(d)
         k_set = plan.extra["set"]["k"]
         key_a = ("a", n, k_set, None if nplan is None else nplan.extra["set"]["k"],
-                 ahead is not None, own["nmax"] > 0, own_ahead is not None)
+                 ahead is not None, own["nmax"] > 0)
         nn_ = 8 * n if next is not None else 0
         ranges = (ptr(next[0]) if next is not None else 0, nn_,
                   ptr(next[1]) if next is not None else 0, nn_, ptr(targets), 4 * n, st, 1)
@@ -507,10 +476,7 @@ class ShardedTrainStep:
                 X.wait_ahead(*ahead)
             else:
                 recv = X.exchange(plan.send, send_splits, recv_splits, slot="recv")
-            if own_ahead is not None:
-                ops.owner_catchup(own)
-            else:
-                ops.owner_prepare(recv, plan, own)
+            ops.owner_prepare(recv, plan, own)
             rows = ops.owner_gather(own, recv)
             back = X.exchange(rows, recv_splits, send_splits, slot="rows")
             res["grads"], res["loss"] = ops.compute(plan, back, user_ids, item_ids, targets,
@@ -524,7 +490,6 @@ class ShardedTrainStep:
             ops.last_loss = res["loss"]
         # the next plan's sizes (for its rows' exchange ahead), then the rest of the step
         nahead = None
-        own_next = None
         if self.ahead and self._pending is not None:
             nxt = self._pending[2]
             X.counts_wait(nxt)
@@ -532,30 +497,21 @@ class ShardedTrainStep:
             nahead = nxt.extra["set"]["k"]
             X.site(f"ahead{nahead}", s_, r_)
             ahead_out = X.exchange_out(nxt.send, r_, f"ahead{nahead}")
-            if self._claims_ahead():
-                own_next = ops.owner_host(nxt)      # (host side; its claim is in segment B)
         grads = res["grads"]
         X.exchange_out(grads, recv_splits, "grads")
-        key_b = ("b", n, k_set, nahead, own["nmax"] > 0, own_next is not None)
+        key_b = ("b", n, k_set, nahead, own["nmax"] > 0)
         sig = self._signature()
-        scalars_b = scalars + ((own_next["token"],) if own_next is not None else (0,))
 
         def seg_b():
             if nahead is not None:
                 self._pending[3] = X.exchange_ahead(self._pending[2])
-                if own_next is not None:
-                    ops.owner_claim(self._pending[3][0], own_next,
-                                    self._pending[2].stream.cuda_stream, SLOT_TOKEN_NEXT)
-                    self._pending[3][1].record(self._pending[2].stream.cuda_stream)
             ar = X.all_reduce_start(ops.dense_grad())
             got = X.exchange(grads, send_splits, recv_splits, slot="grads")
             ops.owner_apply(own, got)
             X.all_reduce_wait(ar)
             ops.dense_step()
-        replayed = T.run(key_b, sig, self._pre(), (0, 0, 0, 0, 0, 0, st, 1), scalars_b, seg_b,
+        replayed = T.run(key_b, sig, self._pre(), (0, 0, 0, 0, 0, 0, st, 1), scalars, seg_b,
                          self._post_b)
-        if own_next is not None:
-            self._pending[4] = own_next
         if replayed:
             if nahead is not None:
                 self._pending[3] = (ahead_out, X._ahead_ev[nahead])
@@ -618,8 +574,7 @@ class HipShardOps:
         self.last_loss = None
         # owner side: claim tokens and row -> unique index, one int32 per local row and kind
         ru, ri = model.num_users, model.num_products
-        # (one set per plan-buffer set: a step's owner claim may run a step ahead, on the plan
-        # stream, while the previous step still reads its own)
+        # (one set per plan-buffer set, taken in turn by consecutive steps)
         self.marks = [[torch.zeros(ru, dtype=torch.int32, device=self.dev),
                        torch.zeros(ri, dtype=torch.int32, device=self.dev)] for _ in range(2)]
         self.uidxs = [[torch.zeros(ru, dtype=torch.int32, device=self.dev),
@@ -745,7 +700,7 @@ class HipShardOps:
     def owner_host(self, plan):
         """Host side of the owner phase of a step: the receive layout (one persistent host
         struct per plan-buffer set), the claim token and the sizes; the buffers sized for them
-        (the per-step ones of the plan's set: its claim may run a step ahead)."""
+        (the per-step ones of the plan's set)."""
         par = plan.extra["set"]["k"]
         L = self._layout(plan.recv_counts, par)
         tu = sum(c[0] for c in plan.recv_counts)
@@ -765,29 +720,24 @@ class HipShardOps:
         return {"layout": L, "uniq": uq, "pos": pos, "nmax": nmax, "token": self.token,
                 "rows": rows, "G": G, "par": par, "cnt": self.cnts[par]}
 
-    def owner_claim(self, recv, own, st, token_slot=SLOT_TOKEN):
-        """The owner's sort-free dedup of the received rows (claim + positions) on stream st."""
+    def owner_prepare(self, recv, plan, own=None):
+        """The owner's sort-free dedup of the received rows (claim + positions), then the claimed
+        rows caught up through the current step; on the step's stream."""
+        own = own or self.owner_host(plan)
         L, uq, pos, par = own["layout"], own["uniq"], own["pos"], own["par"]
         mk, ux = self.marks[par], self.uidxs[par]
-        _lib.call_tagged("ncf_shard_owner_prepare", {2: token_slot}, ptr(recv), ctypes.addressof(L),
+        st = self._st()
+        _lib.call_tagged("ncf_shard_owner_prepare", {2: SLOT_TOKEN}, ptr(recv), ctypes.addressof(L),
                          own["token"], ptr(mk[0]), ptr(mk[1]), ptr(ux[0]), ptr(ux[1]),
                          mk[0].numel(), mk[1].numel(), ptr(uq[0]), ptr(uq[1]), ptr(own["cnt"]),
                          ptr(pos[0]), ptr(pos[1]), ptr(self.err), st)
-
-    def owner_catchup(self, own):
-        """The claimed rows caught up through the current step (on the step's stream)."""
         d = self.deferred
         if own["nmax"] > 0:
             d._ensure(d.t + 1)
-            pairs = self._pairs(own["uniq"])
+            pairs = self._pairs(uq)
             _lib.call_tagged("ncf_adam_pairs_catchup_clock", {4: SLOT_NMAX},
                              ctypes.addressof(pairs), 2, self.D, ptr(own["cnt"]), own["nmax"], 0,
-                             ptr(self.clock), ptr(d._table), *d._consts(), self._st())
-
-    def owner_prepare(self, recv, plan, own=None):
-        own = own or self.owner_host(plan)
-        self.owner_claim(recv, own, self._st())
-        self.owner_catchup(own)
+                             ptr(self.clock), ptr(d._table), *d._consts(), st)
         return own
 
     def _pairs(self, uq, G=None):

@@ -840,17 +840,14 @@ class NCFEngine:
     def backward(self, w: Workspace, uid, iid, grad_prob: Optional[torch.Tensor],
                  targets: Optional[torch.Tensor], drop_p: float, seed: int,
                  loss_denominator: float = 0.0, tables=None, rows=None, uniq=None,
-                 reduce_async: bool = False, bf16: bool = False, grad_rows=None,
-                 table_ld: Optional[int] = None, reduce_side=None, fused_apply=None,
-                 tables_done=None):
+                 bf16: bool = False, grad_rows=None, table_ld: Optional[int] = None,
+                 reduce_side=None, fused_apply=None, tables_done=None):
         """Gradients of every used parameter.  Dense grads land in the flat grad buffer; table
-        grads stay compact (self.pending) for the fused Adam step.  ``reduce_async``: the
-        deferred reductions (every dense gradient) run on a side stream, beside whatever the
-        caller queues next that does not read them (the table Adam); the caller must call
-        ``join_reductions()`` before reading the dense gradients.  ``reduce_side`` (a stream
+        grads stay compact (self.pending) for the fused Adam step.  ``reduce_side`` (a stream
         whose queued work the step joins before its dense Adam): the tower and attention
         reductions run there right after the fused tower/attention backward, beside the
-        embedding backward and the table Adam (join_reductions orders them).  ``fused_apply``
+        embedding backward and the table Adam; the caller must call ``join_reductions()``
+        before reading the dense gradients.  ``fused_apply``
         (DeferredTableAdam.fused_apply_args): the table Adam's apply of this step runs inside the
         embedding backward (ncf_embedding_bwd_reduce_apply_clock; w.applied tells the deferred
         schedule).  ``tables_done()`` is called right after the embedding backward is queued
@@ -982,7 +979,7 @@ class NCFEngine:
         else:
             self._sweep_fork("attn_bwd", w)
             self._attention_bwd_unfused(w, drop_p, seed, joins, st)
-        if reduce_side is not None and fused_ta and not reduce_async:
+        if reduce_side is not None and fused_ta:
             # the dense-gradient reductions of the fused backward on the side stream now, beside
             # the embedding backward and the table Adam (its own scratch; joined before the
             # flat Adam by join_reductions)
@@ -1058,19 +1055,7 @@ class NCFEngine:
             tables_done()
         self.join(dev, joins)
         self._sweep_fork("reduce")
-        if reduce_async:
-            if getattr(self, "_red_side", None) is None:
-                self._red_side = _lib.side_stream(dev)
-                self._red_ev = (torch.cuda.Event(), torch.cuda.Event())
-            side = self._red_side
-            self._red_ev[0].record()
-            side.wait_event(self._red_ev[0])
-            with torch.cuda.stream(side):
-                w.run_reductions(side.cuda_stream)
-            self._red_ev[1].record(side)
-            self._red_pending = True
-        else:
-            w.run_reductions(st)
+        w.run_reductions(st)
         self.pending = w
 
     def _embedding_bwd_split(self, w, uid, iid, tbp, d_rows, st):
@@ -1102,9 +1087,6 @@ class NCFEngine:
 
     def join_reductions(self):
         """The current stream waits for the side-stream reductions of the last backward."""
-        if getattr(self, "_red_pending", False):
-            torch.cuda.current_stream(self.flat.device).wait_event(self._red_ev[1])
-            self._red_pending = False
         if getattr(self, "_early_red_pending", False):
             self._early_red_ev[1].wait(_lib.stream_ptr(self.flat.device))
             self._early_red_pending = False

@@ -153,8 +153,7 @@ class StepTapes:
         eng = self.eng
         d = eng.deferred
         return (w is e.w, eng.pending is None, getattr(w, "dedup_ev", None) is e.dedup_ev,
-                tuple(d._owed), d._joined, eng._zero_cols_of is eng.flat_grad,
-                not getattr(eng, "_red_pending", False))
+                tuple(d._owed), d._joined, eng._zero_cols_of is eng.flat_grad)
 
     def backward(self, w, uid, iid, gp, drop_p, seed):
         """engine.backward(w, uid, iid, gp, None, drop_p, seed) replayed or recorded; False
@@ -192,7 +191,7 @@ class StepTapes:
         with tape.record((uid.data_ptr(), 8 * n, iid.data_ptr(), 8 * n, gp.data_ptr(), 4 * n,
                           st, 1)):
             eng.backward(w, uid, iid, gp, None, drop_p, seed)
-        if tape.valid and not w.slots_set and not getattr(eng, "_red_pending", False):
+        if tape.valid and not w.slots_set:
             e.bwd, e.bwd_pre, e.bwd_post = tape, pre, (tuple(d._owed), d._joined)
             e.step = None
             self.recorded += 1

@@ -38,10 +38,6 @@ DEDUP_FORK = "sweep"
 # Steps of per-step Adam scalars a captured step graph is given before it must be re-captured
 # (the scalar table cannot grow from inside a replay); tests shrink it to force re-captures.
 GRAPH_HORIZON = 1 << 16
-# The dense-gradient reductions on a side stream beside the table Adam's apply (engine.backward
-# reduce_async, a stream of its own; joined before the flat Adam close): measured slower (0.379
-# against 0.288 ms/step: a third stream shares a hardware queue)
-REDUCE_ASYNC = False
 # The fused tower/attention backward's reductions queued on the overlapped sweep's side stream
 # right after that kernel (engine.backward reduce_side), beside the embedding backward and the
 # table Adam; joined before the flat Adam close.  Same bits (the bitwise suite runs it).  Off:
@@ -59,42 +55,12 @@ FUSE_APPLY = True
 # at 128 against 0.2769-0.2794 at 64 (tools/step_ab.py, primed 2 x the period); round 6 (run
 # r06zx, min of 3): 128 0.2653, 192 0.2632, 256 0.2669 — within the runs' spread, 128 stays.
 SWEEP_EVERY = 128
-# The step's join of the side stream (sweep, next sort, late catch-up) after the dense Adam
-# rather than before it: the flat Adam (ncf_adam_flat_clock) runs first, then the join, then the
-# clock advance (ncf_step_clock_advance) that the side kernels must not see early.  A join whose
-# event is still pending costs the queue ~10 us after the signal (tools/event_cost.py); placed
-# later, the side work is usually complete when the queue reaches it.  Off: measured neutral
-# (3 interleaved runs each, 0.2706 / 0.2714 against 0.2706 / 0.2707 ms/step: the separate
-# clock-advance launch costs what the later join saves)
-SPLIT_CLOSE = False
 # Trainer.train_epoch runs loss.backward() on the calling thread (torch's autograd otherwise hands
 # every backward of CUDA tensors to a per-device worker thread and waits for it: two thread
 # wake-ups per step, on a host that is the bottleneck of this loop).  The reference loop at C2
 # (tools/dropin_host.py, run r06p): 0.368 -> 0.317 ms/step.  Scoped to the epoch (the
 # torch.autograd.set_multithreading_enabled context manager); the numbers are the same bits.
 CALLING_THREAD_BACKWARD = True
-# The late catch-up of the next batch's rows (deferred.LATE_CATCHUP) left running past the step:
-# the step's join before the clock advance waits for the sweep and the sort only, the late
-# catch-up reads its target from a copy of the clock taken before that join, and the next user
-# of the tables waits for it (deferred.late_join: the next prepare, a flush, a sync).  Without
-# it the step's stream reached that join before the catch-up (~30 us, queued behind the apply)
-# was done and resumed ~10 us after it (rocprof r06k: an 11.5 us gap before the flat Adam).
-# Off: measured neutral (run r06zf, 3 interleaved runs each: min 0.2726 ms/step on, 0.2713 off;
-# the gap moves to the next step's prepare, where the catch-up is still running beside the
-# forward's head).  Bitwise-green either way (the late catch-up / early catch-up tests).
-LATE_DETACHED = False
-# The side stream's work of a step queued at the step's entry, off the step's queue: the next
-# batch's id sort, then the rolling sweep owed by the closed step, their step targets read from a
-# side copy of the clock set from the host's counter (deferred.side_clock), and the late catch-up
-# at the table apply as before, from the same copy.  The step's stream records one event (the
-# table apply done) and waits once (for the late catch-up, before the next gather): no fork
-# event at the tower, no join before the clock advance.  Three dedup sets (the sort at the entry
-# of step T + 1 writes the set of step T - 1, whose reductions are queued before the event the
-# side stream waited for in step T).  Off: measured slower (run r06zj, tools/step_ab.py, 3
-# interleaved runs each: C2 min 0.2795 against 0.2698 ms/step, B = 256 0.1669 against 0.1637 —
-# the sweep beside the reductions and the next gather runs longer than beside the fused forward
-# (64 against 50 us), more than the fork event it saves); bit-identical (its tests run it).
-SIDE_AHEAD = False
 
 
 def _join_side_streams(dev, streams):
@@ -193,7 +159,8 @@ class FusedTrainStep:
         self._static = None
         self._w = None
         self._eager_steps = 0
-        # side streams whose work may outlive a step (SIDE_AHEAD; the dedup fork at "entry"):
+        self._late_next = None     # the late catch-up this step's prefetch left for _tables_done
+        # side streams whose work may outlive a step (the dedup fork at "entry"):
         # when the step is dropped, the stream it was built on waits for them before the
         # caching allocator can hand their buffers (the model's, this step's) to new work there
         self._side_streams = []
@@ -224,26 +191,19 @@ class FusedTrainStep:
         prep = self.deferred.prepare if self.deferred is not None else None
         w = eng.forward(user_ids, item_ids, M, True, drop_p, seed, prepare=prep,
                         tables=self.tables_lp, bf16=self.bf16)
-        # (REDUCE_ASYNC: the dense-gradient reductions beside the table Adam)
         d = self.deferred
         side = (d.side_stream() if EARLY_REDUCE and d is not None and d.overlap and not self.graph
-                and not REDUCE_ASYNC else None)
+                else None)
         fa = d.fused_apply_args(w) if FUSE_APPLY and d is not None else None
         # (the late catch-up is read when the table apply has been queued, not here: the sweep
         # fork, and with it the next batch's prefetch, may sit in the backward — "mlp_bwd")
         done = self._tables_done if fa is not None else None
         eng.backward(w, user_ids, item_ids, None, targets, drop_p, seed, tables=self.tables_lp,
-                     bf16=self.bf16, reduce_async=REDUCE_ASYNC and not self.graph,
-                     reduce_side=side, fused_apply=fa, tables_done=done)
+                     bf16=self.bf16, reduce_side=side, fused_apply=fa, tables_done=done)
         st = _lib.stream_ptr(eng.flat.device)
         b1, b2 = self.betas
-        split = (SPLIT_CLOSE and self.deferred is not None and self.clock is not None
-                 and not self.graph and self.deferred.overlap)
-        # (SIDE_AHEAD: no join of the side stream in the step unless a sweep part reading the
-        # live clock was forked in it — the closed step's sweep could not run at the entry)
-        free = self._ahead() and not d._live_pending
         if self.deferred is not None:
-            self.deferred.apply(w, st, late_join=split or free)
+            self.deferred.apply(w, st)
         elif self.bf16:      # dense bf16 sweep (the reference schedule of the bf16 tables)
             D = self.model.mlp_embedding_dim
             for key, lp in self.tables_lp.items():
@@ -258,15 +218,8 @@ class FusedTrainStep:
             key_of = {id(p): k for k, p in self.tables.items()}
             eng.adam_tables(hp, lambda p: self.state[key_of[id(p)]], float(self.step_count + 1), st)
         eng.join_reductions()
-        if self.clock is not None and split:
-            _lib.call("ncf_adam_flat_clock", ptr(eng.flat), ptr(eng.flat_grad), ptr(self.m_flat),
-                      ptr(self.v_flat), eng.flat.numel(), ptr(self.deferred._table), 1,
-                      ptr(self.clock), b1, b2, self.eps, self.wd, st)
+        if self.clock is not None:
             self.deferred.sweep_join()       # (the clock advance below changes its target)
-            _lib.call("ncf_step_clock_advance", ptr(self.clock), self.base_seed, st)
-        elif self.clock is not None:
-            if self.deferred is not None and not free:
-                self.deferred.sweep_join()   # (the clock advance below changes its target)
             _lib.call("ncf_adam_flat_clock_close", ptr(eng.flat), ptr(eng.flat_grad),
                       ptr(self.m_flat), ptr(self.v_flat), eng.flat.numel(),
                       ptr(self.deferred._table), 1, ptr(self.clock), b1, b2, self.eps, self.wd,
@@ -284,12 +237,6 @@ class FusedTrainStep:
         late, self._late_next = self._late_next, None
         if late is not None:
             self._late_catchup(*late)
-        elif self._ahead():      # (the closed step's sweep may then run at the next entry)
-            d = self.deferred
-            ev = self._event()
-            ev.record(_lib.stream_ptr(self.model.engine.flat.device))
-            ev.wait(d.side_stream().cuda_stream)
-            d.side_ordered()
 
     def _late_catchup(self, s, n):
         """deferred.LATE_CATCHUP: the next batch's rows (dedup set s, sorted on the side stream)
@@ -298,38 +245,16 @@ class FusedTrainStep:
         (before the clock advance) waits for it."""
         d = self.deferred
         side = d.side_stream()
-        clk = None
-        ahead = self._ahead()
-        if LATE_DETACHED and not ahead and d._late_clock is None:
-            d._late_clock = torch.zeros_like(self.clock)
-        ev = self._event()     # (also orders the copy below after the copy buffer's creation)
+        ev = self._event()
         ev.record(_lib.stream_ptr(self.model.engine.flat.device))
         ev.wait(side.cuda_stream)
-        if ahead:
-            d.side_ordered()
-            clk = d.side_clock(side.cuda_stream)
-        elif LATE_DETACHED:
-            # the clock as this step's catch-up needs it, copied on the side stream ahead of the
-            # step's join (the advance after that join cannot overtake the copy)
-            clk = d._late_clock
-            _lib.call("ncf_memcpy_async", ptr(clk), ptr(self.clock), 16, side.cuda_stream)
-            d.sweep_done(side.cuda_stream)
-            d._joined = False
         if _lib.PROFILE is not None:     # (the per-launch instrumentation times it on its stream)
             with torch.cuda.stream(side):
-                d.late_catchup(s, n, side.cuda_stream, clk)
+                d.late_catchup(s, n, side.cuda_stream)
         else:
-            d.late_catchup(s, n, side.cuda_stream, clk)
-        if LATE_DETACHED or ahead:
-            evs = getattr(self, "_late_evs", None)
-            if evs is None:
-                evs = self._late_evs = [_lib.RawEvent(stream_only=True) for _ in range(2)]
-            evs.reverse()
-            evs[0].record(side.cuda_stream)
-            d._late_ev = evs[0]
-        else:
-            d.sweep_done(side.cuda_stream)
-            d._joined = False
+            d.late_catchup(s, n, side.cuda_stream)
+        d.sweep_done(side.cuda_stream)
+        d._joined = False
 
     # ---- pipelined dedup: the id sort of step t+1 runs on a side stream under step t
     def _event(self):
@@ -342,27 +267,19 @@ class FusedTrainStep:
         return ring[0][ring[1]]
 
     def _dedup_sets(self, w):
-        """A ring of sets of the dedup outputs (sorted segments, unique ids, counts) for
-        workspace w, used in turn by consecutive steps: the workspace's own buffers and a twin
-        (a third with SIDE_AHEAD).  {"ring": [...], "i": the current step's set}."""
-        k = 3 if self._ahead() else 2
-        sets = w.cache.get(("dedup_sets", k))
+        """The two sets of the dedup outputs (sorted segments, unique ids, counts) for workspace
+        w, used in turn by consecutive steps: the workspace's own buffers and a twin.
+        {"ring": [...], "i": the current step's set}."""
+        sets = w.cache.get("dedup_sets")
         if sets is None:
             a = dict(emb_ws=w.emb_ws, uniq_u=w.uniq_u, uniq_i=w.uniq_i, num_unique=w.num_unique)
-            ring = [a] + [{n: torch.empty_like(v) for n, v in a.items()} for _ in range(k - 1)]
-            sets = w.cache[("dedup_sets", k)] = {"ring": ring, "i": 0}
+            ring = [a, {n: torch.empty_like(v) for n, v in a.items()}]
+            sets = w.cache["dedup_sets"] = {"ring": ring, "i": 0}
         return sets
 
     @staticmethod
     def _next_set(sets):
         return sets["ring"][(sets["i"] + 1) % len(sets["ring"])]
-
-    def _ahead(self):
-        """SIDE_AHEAD applies: eager, the overlapped sweep, the late catch-up behind the fused
-        table apply (deferred.EARLY_CATCHUP = False)."""
-        d = self.deferred
-        return (SIDE_AHEAD and not self.graph and d is not None and d.overlap and FUSE_APPLY
-                and deferred_mod.LATE_CATCHUP and deferred_mod.EARLY_CATCHUP is False)
 
     def _prefetch_dedup(self, w, uid, iid, entry, side=None):
         """Dedup of the NEXT step's ids into the idle set, on the side stream, after `entry`
@@ -391,22 +308,6 @@ class FusedTrainStep:
         entry.wait(side.cuda_stream)
         self._enqueue_dedup(s, w, uid, iid, side)
 
-    def _entry_side(self, w, uid, next):
-        """SIDE_AHEAD, at the step's entry, on the deferred schedule's side stream (ordered
-        after the previous step's table apply by its tables-done event, nothing recorded on the
-        step's stream): the next batch's id sort into the next set of the ring, then the
-        rolling sweep the previous step owes (deferred.sweep_owed, its target from the side
-        clock)."""
-        d = self.deferred
-        side = d.side_stream()
-        d.side_clock(side.cuda_stream)
-        if next is not None and next[0].numel() == uid.numel():
-            s = self._next_set(self._dedup_sets(w))
-            self._enqueue_dedup(s, w, next[0], next[1], side)
-            self._late_next = (s, next[0].numel())
-        if d.sweep_owed(side.cuda_stream):
-            self.model.engine.fork_hook = None
-
     def _enqueue_dedup(self, s, w, uid, iid, side):
         m = self.model
         u = uid.reshape(-1)
@@ -419,7 +320,7 @@ class FusedTrainStep:
         ev.record(side.cuda_stream)
         self._pending = (uid, iid, ev)          # the caller's objects: matched by identity
 
-    def _activate_dedup(self, w, uid, iid, ahead=False):
+    def _activate_dedup(self, w, uid, iid):
         """Point w at this step's dedup set: the prefetched one when it was made for these ids
         (the step then waits for its event instead of sorting), else the next set, sorted
         inline by the deferred Adam's prepare."""
@@ -435,10 +336,8 @@ class FusedTrainStep:
             mine = pend[0] is uid and pend[1] is iid
             if pend[2] is None:               # sorted behind the sweep: joined with it
                 self.deferred.sweep_join()
-            elif not (ahead and mine and late_t is not None):
+            else:
                 pend[2].wait(cur.cuda_stream)  # (also orders a stale prefetch before reuse)
-            # (else: the late catch-up queued behind that sort, which the step's prepare
-            # waits for, orders it — deferred.late_join)
             if mine:
                 w.prededuped = True
                 w.late_t = late_t
@@ -450,19 +349,16 @@ class FusedTrainStep:
         call must pass those very tensor objects, unmodified, to use the prefetched sort."""
         m = self.model
         M = M or (1 + m.negative_samples)
-        self._late_next = None     # set by this step's prefetch (_prefetch_dedup / _entry_side)
+        self._late_next = None     # set by this step's prefetch (_prefetch_dedup)
         if not self.graph:
             pipe = self.deferred is not None and self.clock is not None and (
                 next is not None or getattr(self, "_pending", None) is not None)
-            ahead = self._ahead()
             if pipe:
                 eng = m.engine
                 eng.ensure_layout()
                 w0 = eng.workspace(user_ids.numel(), M, True)
-                self._activate_dedup(w0, user_ids, item_ids, ahead)
-                if ahead:
-                    self._entry_side(w0, user_ids, next)
-                elif next is not None and next[0].numel() == user_ids.numel():
+                self._activate_dedup(w0, user_ids, item_ids)
+                if next is not None and next[0].numel() == user_ids.numel():
                     if DEDUP_FORK == "entry":
                         # (recorded only here: an event record costs the queue a few us)
                         entry = self._event()
@@ -537,6 +433,7 @@ class FusedTrainStep:
     def eager(self, user_ids, item_ids, targets, M: Optional[int] = None):
         """One step through the launch sequence itself (never the captured graph) — the same
         kernels a replay runs; used for per-launch instrumentation."""
+        self._late_next = None     # (no prefetch runs here: nothing left for _tables_done)
         w = self._body(user_ids, item_ids, targets, M or (1 + self.model.negative_samples))
         self.step_count += 1
         self.model.engine.updates += 1

@@ -565,7 +565,7 @@ def test_reduce_batch_vec_lanes_bitwise_equal_scalar():
     outs0 = [torch.randn(((L + cols - 1) // cols) * (cols + 2), generator=g).to(DEV)
              for P, L, stride, off, cols, *_ in specs]
     res = []
-    for vec in (0, 1, 2):
+    for vec in (0, 1):
         prev = _lib.query("ncf_reduce_set_vec", vec)
         try:
             lst = _lib.ReduceList()
@@ -1208,9 +1208,7 @@ def test_late_catchup_bitwise_equals_dense(monkeypatch):
     """The next batch's catch-up queued behind this step's fused table apply, beside the
     dense-gradient reductions (deferred.LATE_CATCHUP), and the next step skipping its own
     catch-up, against the dense schedule bit for bit (dropout, sweep every 8 steps); and against
-    the late catch-up off, and the step's side-stream join after the flat Adam instead of before
-    it (trainer.SPLIT_CLOSE: apply(late_join) -> ncf_adam_flat_clock -> sweep_join -> the separate
-    clock advance).  The skip must have happened on every step but the first (deferred
+    the late catch-up off.  The skip must have happened on every step but the first (deferred
     late_skips), with the sweep forked at the default point of this geometry and in the backward
     ("mlp_bwd": the prefetch, and the late catch-up, queued after the forward)."""
     import ncf_amd.deferred as Dm
@@ -1237,9 +1235,6 @@ def test_late_catchup_bitwise_equals_dense(monkeypatch):
     for drop in (0.2, 0.0):
         pairs.append([run(late, dropout=drop) for late in (True, False)])
     pairs.append([pairs[1][0], _fused_run(False, 30)])   # (the dense schedule: no dropout)
-    monkeypatch.setattr(Tr, "SPLIT_CLOSE", True)       # the side stream joined after the flat Adam
-    pairs.append([pairs[0][0], run(True, dropout=0.2)])
-    monkeypatch.setattr(Tr, "SPLIT_CLOSE", False)
     monkeypatch.setattr(Dm, "SWEEP_FORK", "mlp_bwd")    # the prefetch inside the backward
     pairs.append([pairs[0][0], run(True, dropout=0.2)])
     for (b_sd, b_m), (a_sd, a_m) in pairs:
@@ -1249,66 +1244,48 @@ def test_late_catchup_bitwise_equals_dense(monkeypatch):
             assert torch.equal(a_m[k][0], b_m[k][0]) and torch.equal(a_m[k][1], b_m[k][1]), k
 
 
-@pytest.mark.parametrize("tables", ["fp32", "bf16"])
-def test_side_ahead_bitwise_equals_dense(monkeypatch, tables):
-    """trainer.SIDE_AHEAD: the next batch's sort and the closed step's rolling sweep queued on the
-    side stream at the step's entry (their targets from the side clock, ncf_step_clock_set), the
-    late catch-up behind the table apply from the same clock, no fork event and no join of the
-    side stream in the step (three dedup sets).  Against the default schedule bit for bit —
-    parameters and both moments, dropout on, sweep every 8 steps, 30 steps (fp32 tables: also
-    the dense schedule through the default one, test_late_catchup_bitwise_equals_dense).  The
-    sweep must have run at the entry on every step after the second, the late catch-up's skip
-    on every step after the first, and no sweep part forked at an engine fork point."""
-    import ncf_amd.deferred as Dm
-    import ncf_amd.trainer as Tr
-    dt = torch.bfloat16 if tables == "bf16" else torch.float32
-    kw = dict(sweep_every=8, dropout=0.2, clock=True, overlap_sweep=True, pipelined=True,
-              table_dtype=dt)
-    monkeypatch.setattr(Dm, "EARLY_CATCHUP", False)     # (SIDE_AHEAD rides the late catch-up)
-    ref = _fused_run(True, 30, **kw)
-    seen, owed, forks = [], [], []
-    orig_p, orig_o, orig_f = (Dm.DeferredTableAdam.prepare, Dm.DeferredTableAdam.sweep_owed,
-                              Dm.DeferredTableAdam.sweep_fork)
-
-    def prep(self, *a):
-        seen.append(self)
-        return orig_p(self, *a)
-
-    def sw(self, *a):
-        r = orig_o(self, *a)
-        owed.append(r)
-        return r
-
-    def fk(self, *a, **k):
-        n = len(self._owed)
-        r = orig_f(self, *a, **k)
-        forks.append(n - len(self._owed))
-        return r
-    monkeypatch.setattr(Dm.DeferredTableAdam, "prepare", prep)
-    monkeypatch.setattr(Dm.DeferredTableAdam, "sweep_owed", sw)
-    monkeypatch.setattr(Dm.DeferredTableAdam, "sweep_fork", fk)
-    monkeypatch.setattr(Tr, "SIDE_AHEAD", True)
-    got = _fused_run(True, 30, **kw)
-    assert max(d.late_skips for d in seen) >= 28
-    assert sum(owed) >= 28 and sum(forks) == 0, (owed, forks)
-    for k in ref[0]:
-        assert torch.equal(ref[0][k], got[0][k]), k
-    for k in ref[1]:
-        assert torch.equal(ref[1][k][0], got[1][k][0]) and torch.equal(ref[1][k][1], got[1][k][1]), k
-
-
-@pytest.mark.parametrize("ahead", [False, True])
-def test_pipelined_dedup_bitwise_equals_inline(monkeypatch, ahead):
-    """FusedTrainStep(next=...) sorts the next batch's ids on a side stream under the current
-    step (two alternating dedup buffer sets; three with trainer.SIDE_AHEAD, the sort queued at
-    the step's entry); results are bit for bit those of the inline sort, including a step whose
-    prefetch is discarded (ids not the ones announced) and a step told no next batch."""
-    import ncf_amd.deferred as Dm
-    import ncf_amd.trainer as Tr
+def test_eager_on_fresh_step():
+    """FusedTrainStep.eager() as the first call ever on a step (no __call__ before it: the late
+    catch-up hand-over starts empty) against a twin whose first call was step(): parameters and
+    Adam moments bit for bit, after that call and two ordinary steps (dropout on, B = 61 groups
+    of 5: the last workgroup ragged)."""
     from ncf_amd.trainer import FusedTrainStep
-    monkeypatch.setattr(Tr, "SIDE_AHEAD", ahead)
-    if ahead:
-        monkeypatch.setattr(Dm, "EARLY_CATCHUP", False)
+    U, I, B = 3000, 500, 61
+    g = torch.Generator().manual_seed(29)
+    batches = []
+    for _ in range(3):
+        u = torch.randint(0, U, (B,), generator=g).repeat_interleave(5).to(DEV)
+        i = torch.randint(0, I, (B * 5,), generator=g).to(DEV)
+        t = torch.zeros(B, 5)
+        t[:, 0] = 1
+        batches.append((u, i, t.reshape(-1, 1).to(DEV)))
+    out = []
+    for eager in (True, False):
+        torch.manual_seed(13)
+        m = ncf.AdvancedNCF(U, I, 5, 24, 64, 64, 32, [256, 128, 64], 4, 0.2, 4).to(DEV)
+        step = FusedTrainStep(m, lr=1e-3, weight_decay=1e-5)
+        (step.eager if eager else step)(*batches[0])
+        for u, i, t in batches[1:]:
+            step(u, i, t)
+        step.sync()
+        out.append(({k: v.detach().cpu().clone() for k, v in m.state_dict().items()},
+                    {k: (v["exp_avg"].cpu().clone(), v["exp_avg_sq"].cpu().clone())
+                     for k, v in step.state.items()},
+                    step.m_flat.cpu().clone(), step.v_flat.cpu().clone()))
+    (a_sd, a_m, a_mf, a_vf), (b_sd, b_m, b_mf, b_vf) = out
+    for k in a_sd:
+        assert torch.equal(a_sd[k], b_sd[k]), k
+    for k in a_m:
+        assert torch.equal(a_m[k][0], b_m[k][0]) and torch.equal(a_m[k][1], b_m[k][1]), k
+    assert torch.equal(a_mf, b_mf) and torch.equal(a_vf, b_vf)
+
+
+def test_pipelined_dedup_bitwise_equals_inline():
+    """FusedTrainStep(next=...) sorts the next batch's ids on a side stream under the current
+    step (two alternating dedup buffer sets); results are bit for bit those of the inline sort,
+    including a step whose prefetch is discarded (ids not the ones announced) and a step told no
+    next batch."""
+    from ncf_amd.trainer import FusedTrainStep
     U, I, B = 3000, 500, 64
     g = torch.Generator().manual_seed(21)
     batches = []
@@ -1437,19 +1414,16 @@ def test_step_teardown_with_side_work_queued_then_new_step():
 
     ref = _fused_run(True, 12, sweep_every=8, B=B, seed=31, dropout=0.2, clock=True,
                      overlap_sweep=True, pipelined=True)
-    for fork, early, ahead in (("sweep", False, False), ("entry", True, False),
-                               ("sweep", False, True)):
-        old = (Tr.DEDUP_FORK, Tr.EARLY_REDUCE, Tr.SIDE_AHEAD, _D.EARLY_CATCHUP)
-        Tr.DEDUP_FORK, Tr.EARLY_REDUCE, Tr.SIDE_AHEAD = fork, early, ahead
-        if ahead:
-            _D.EARLY_CATCHUP = False
+    for fork, early in (("sweep", False), ("entry", True)):
+        old = (Tr.DEDUP_FORK, Tr.EARLY_REDUCE)
+        Tr.DEDUP_FORK, Tr.EARLY_REDUCE = fork, early
         try:
             leave_in_flight(7)       # (its objects are unreachable on return: freed now)
             gc.collect()
             got = _fused_run(True, 12, sweep_every=8, B=B, seed=31, dropout=0.2, clock=True,
                              overlap_sweep=True, pipelined=True)
         finally:
-            Tr.DEDUP_FORK, Tr.EARLY_REDUCE, Tr.SIDE_AHEAD, _D.EARLY_CATCHUP = old
+            Tr.DEDUP_FORK, Tr.EARLY_REDUCE = old
         for k in ref[0]:
             assert torch.equal(ref[0][k], got[0][k]), (fork, k)
         for k in ref[1]:
@@ -1723,14 +1697,6 @@ def test_sharded_step_c3_size_world1_bitwise_equals_fused():
     sort of 1M-row keys, hot items whose segments span many pieces, the received rows read in
     place — bit for bit the fused step over 6 steps (4 of them pipelined)."""
     _sharded_vs_fused("rccl", True, U=1_000_000, I=100_000, Bg=4096, steps=6, check_hot=True)
-
-
-def test_sharded_step_claim_ahead_bitwise_equals_fused(monkeypatch):
-    """The owner claim of the next step's rows run a step ahead on the plan stream
-    (distributed.CLAIM_AHEAD, off by default): the same bits as the fused step."""
-    import ncf_amd.distributed as Dist
-    monkeypatch.setattr(Dist, "CLAIM_AHEAD", True)
-    test_sharded_step_world1_bitwise_equals_fused("rccl", True)
 
 
 def test_comm_alltoallv_and_allreduce_single_rank():
