@@ -1,0 +1,452 @@
+"""Training with dropout ON against the float64 CPU oracle (oracle/ncf_oracle.py), on the MI355X.
+
+Every other comparison with the oracle or the goldens runs at dropout 0, and every other test
+with dropout > 0 holds two HIP forms of one step to each other.  Here the dropout stream is
+restated on the host (tests/dropout_stream.py, plain numpy, from the device code's definition),
+the kernels' keep-scales are held to it bit for bit, and the oracle runs the same step in
+float64 with those masks: probabilities, loss, every dense gradient, the compact table gradients
+and the parameters after Adam, at the tolerances of test_gpu_parity.test_train_vs_oracle:
+
+    prob < 5e-6, loss < 5e-6, gradients rtol 2e-4 / atol 2e-6, parameters through
+    tests/parity.py's sign-flip zones with atol 5e-6.
+
+None of these is fitted to the GPU's output.  Their headroom was measured on the CPU with the
+fp32 oracle against the float64 oracle on the same masks, per case (the figures stand beside
+each case below): the fp32 oracle stays within a quarter of every tolerance.  ReLU kinks do not
+decide a comparison: in the float64 oracle no tower pre-activation is closer to 0 than 4 x the
+largest fp32-vs-float64 pre-activation difference measured for that case (``pre``, asserted).
+
+Also here: the standalone MultiHeadAttention in training mode (attention.hip's LMAX 8 and 64
+forms, masked and not) against O.mha(..., drop_mask=...) in float64.
+"""
+import numpy as np
+import pytest
+import torch
+
+import _ncf_pkg
+from oracle import ncf_oracle as O
+from tests import dropout_stream as S
+from tests.conftest import sub
+from tests.parity import assert_params_close, zone_from_grads
+
+pytestmark = pytest.mark.gpu
+ncf = _ncf_pkg.load()
+DEV = torch.device("cuda:0")
+
+U, I, HID, TDIM, LR, WD = 400, 300, [256, 128, 64], 32, 1e-3, 1e-5
+INIT_SEED = 21
+TABLE_KEYS = {"mf_user": O.K_MF_U, "mf_item": O.K_MF_I, "mlp_user": O.K_MLP_U, "mlp_item": O.K_MLP_I}
+
+# name: D, H, M, B, p, steps, kind, engine switches, data seed, and the CPU-side measurements
+# of that case (fp32 oracle against the float64 oracle on the same masks, one host thread):
+#   pre  = largest |fp32 - fp64| tower pre-activation (the kink margin is 4 x this);
+#   the comment gives max |dprob|, |dloss|, the worst gradient element as a fraction of
+#   2e-6 + 2e-4 |g|, and the smallest float64 |pre-activation| of the case.
+# kind: "clock" = FusedTrainStep's default (deferred tables, device step clock: the step's seed
+# is read from the clock); "host" = FusedTrainStep(deferred=False) (the seed drawn on the host
+# each step); "reference" = model(kjt) -> BCE -> backward() -> torch.optim.Adam.step() (the
+# first forward's seed drawn on the host, later ones from the clock the fused Adam attaches).
+def _case(D, H, M, B, p, steps, kind, form, sw, data_seed, pre, **kw):
+    return dict(D=D, H=H, M=M, B=B, p=p, steps=steps, kind=kind, form=form, sw=sw,
+                data_seed=data_seed, pre=pre, **kw)
+
+
+# form: what the step runs ("fused_small" / "fused_80": attention + tower in one launch per
+# direction, small-batch or 80-row tiles; "block": the attention block and the tower's own
+# launch; "unfused": projection GEMMs + attention.hip core + per-layer tower launches).
+_UNFUSED = {"ATTN_BLOCK": False, "MLP_FUSED": False, "MLP_WGRAD": False}
+_FP32_TOWER = {"BF16_MM": False}
+CASES = {
+    # the default step, 3 consecutive steps, each on its clock seed
+    # CPU: |dprob| 1.59e-7, |dloss| 6.0e-8, gradient at 0.014 of its tolerance; nearest 8.35e-6
+    "default": _case(64, 4, 5, 37, 0.2, 3, "clock", "fused_small", {}, 1696, 1.68e-6),
+    # CPU: 1.38e-7, 9.0e-8, 0.010; nearest 8.16e-6
+    "tiles80": _case(64, 4, 5, 37, 0.2, 2, "clock", "fused_80", {"SMALL_TILE_GROUPS": 0}, 739,
+                     1.69e-6),
+    # the three host-seeded forms share seeds and data.  CPU: 1.55e-7, 1.5e-8, 0.010; nearest 7.16e-6
+    "unfused": _case(64, 4, 5, 37, 0.2, 2, "host", "unfused", _UNFUSED, 410, 1.75e-6),
+    "block_stash": _case(64, 4, 5, 37, 0.2, 2, "host", "block",
+                         {"FUSE_ATTN_TOWER": False, "ATTN_RC": False}, 410, 1.75e-6),
+    "block_rc": _case(64, 4, 5, 37, 0.2, 2, "host", "block",
+                      {"FUSE_ATTN_TOWER": False, "ATTN_RC": True}, 410, 1.75e-6),
+    # the reference call pattern.  CPU: 1.37e-7, 2.2e-8, 0.011; nearest 6.74e-6
+    "reference": _case(64, 4, 5, 37, 0.2, 2, "reference", "fused_small", {}, 142, 1.56e-6),
+    # one head, M = 3.  CPU: 1.46e-7, 2.7e-8, 0.011; nearest 6.30e-6
+    "h1_m3": _case(64, 1, 3, 50, 0.2, 2, "clock", "block", {}, 395, 1.42e-6),
+    # M = 1: one key per row, whole attention weights dropped or doubled (p = 0.5)
+    # CPU: 1.78e-7, 3.6e-8, 0.035; nearest 6.58e-6
+    "m1": _case(64, 4, 1, 20, 0.5, 2, "clock", "block", {}, 44, 1.57e-6),
+    # the C4 dims, padding rows inside a tile.  CPU: 1.71e-7, 5.5e-8, 0.015; nearest 1.22e-5
+    "d128": _case(128, 8, 6, 19, 0.2, 2, "clock", "block", {}, 513, 2.01e-6),
+    # bf16 tables under the fp32 tower, one step (tests/test_gpu_bf16.py), the reference on the
+    # widened bf16 tables.  CPU: 1.74e-7, 1.44e-7, 0.014; nearest 1.33e-5
+    "bf16_d64_p0": _case(64, 4, 5, 37, 0.0, 1, "host", "fused_small", _FP32_TOWER, 1, 1.52e-6,
+                         table_dtype="bf16"),
+    # CPU: 1.81e-7, 9.3e-8, 0.012; nearest 6.41e-6
+    "bf16_d64_p02": _case(64, 4, 5, 37, 0.2, 1, "host", "fused_small", _FP32_TOWER, 1, 1.54e-6,
+                          table_dtype="bf16"),
+    # CPU: 1.15e-7, 1.3e-8, 0.020; nearest 4.94e-5
+    "bf16_d128_p0": _case(128, 8, 6, 19, 0.0, 1, "host", "block", _FP32_TOWER, 2, 1.42e-6,
+                          table_dtype="bf16"),
+    # CPU: 1.15e-7, 7.2e-8, 0.016; nearest 7.56e-6
+    "bf16_d128_p02": _case(128, 8, 6, 19, 0.2, 1, "host", "block", _FP32_TOWER, 4, 1.79e-6,
+                           table_dtype="bf16"),
+}
+
+
+def make_model(D, H, M, p):
+    torch.manual_seed(INIT_SEED)
+    return ncf.AdvancedNCF(U, I, 5, 24, D, D, TDIM, HID, H, p, M - 1)
+
+
+def make_batches(B, M, steps, data_seed):
+    """Zipf-ish items (hot ids repeat: long segments), as test_train_vs_oracle."""
+    g = torch.Generator().manual_seed(data_seed)
+    out = []
+    for _ in range(steps):
+        u = torch.randint(0, U, (B,), generator=g).repeat_interleave(M)
+        i = (torch.rand(B * M, generator=g) ** 3 * I).long().clamp_max(I - 1)
+        t = torch.zeros(B, M)
+        t[:, 0] = 1
+        out.append((u, i, t.reshape(-1, 1)))
+    return out
+
+
+def host_seed(k):
+    """The seed the next host-seeded step draws (torch.randint(0, 2**62, (1,)) on the default
+    generator): seed the generator, draw once, seed it again, so that the step draws the same."""
+    torch.manual_seed(k)
+    s = int(torch.randint(0, 2 ** 62, (1,)).item())
+    torch.manual_seed(k)
+    return s
+
+
+def torch_masks(seed, B, H, M, p, dtype=torch.float64):
+    m = S.step_masks(seed, B, H, M, HID, p)
+    return {"attn": torch.from_numpy(m["attn"]).to(dtype),
+            "mlp": [torch.from_numpy(x).to(dtype) for x in m["mlp"]]}
+
+
+def cast_state(sd, dtype):
+    return {k: (v.detach().clone().to(dtype) if v.is_floating_point() else v.detach().clone())
+            for k, v in sd.items()}
+
+
+def tower_preacts(p, u, i, M, H, masks):
+    """The tower's pre-activations (the Linear outputs the ReLUs see) of the oracle's training
+    forward, from the oracle's own pieces."""
+    n = u.numel()
+    g, b = p["mlp_norm.weight"], p["mlp_norm.bias"]
+    xu = O.layer_norm(p[O.K_MLP_U][u], g, b).view(n // M, M, -1)
+    xi = O.layer_norm(p[O.K_MLP_I][i], g, b).view(n // M, M, -1)
+    att = O.mha(p, O.ATT, xu, xi, xi, H, masks["attn"]).reshape(n, -1)
+    x = torch.cat([att, torch.zeros(n, TDIM, dtype=att.dtype)], 1)
+    out = []
+    for l in range(len(HID)):
+        z = O.linear(x, p[f"mlp.{4 * l}.weight"], p[f"mlp.{4 * l}.bias"])
+        out.append(z)
+        x = O.layer_norm(torch.relu(z), p[f"mlp.{4 * l + 2}.weight"], p[f"mlp.{4 * l + 2}.bias"])
+        x = x * masks["mlp"][l]
+    return out
+
+
+def oracle_run(init, batches, seeds, H, M, p, dtype=torch.float64):
+    """The oracle's trajectory over ``batches`` with the masks of ``seeds`` (one per step), on
+    one host thread (test_gpu_fullsize: torch's threaded CPU reductions do not fix their order).
+    Per step: prob, loss, grads, the parameters before the step, the pre-activations."""
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        ref = cast_state(init, dtype)
+        opt = O.AdamState(lr=LR, weight_decay=WD)
+        rec = []
+        for (u, i, t), seed in zip(batches, seeds):
+            masks = torch_masks(seed, u.numel() // M, H, M, p, dtype)
+            before = {k: v.clone() for k, v in ref.items()}
+            with torch.no_grad():
+                pre = tower_preacts(ref, u, i, M, H, masks)
+            prob, loss, grads = O.train_step(ref, opt, u, i, t.to(dtype), negative_samples=M - 1,
+                                             num_heads=H, temporal_dim=TDIM, n_layers=len(HID),
+                                             dropout_masks=masks)
+            rec.append(dict(prob=prob, loss=loss, grads=grads, before=before, pre=pre))
+        return rec, ref
+    finally:
+        torch.set_num_threads(threads)
+
+
+def case_seeds(name, steps):
+    """The seeds a case's steps will use, worked out without a GPU (the CPU-side measurements
+    are taken with them, tests/test_dropout_stream.py; the GPU tests assert them): host-seeded steps reseed the default generator with 1000 + s;
+    under the clock the base seed is the draw that follows the model's construction."""
+    c = CASES[name]
+    if c["kind"] == "clock":
+        make_model(c["D"], c["H"], c["M"], c["p"])
+        base = int(torch.randint(0, 2 ** 62, (1,)).item())
+        return [S.clock_seed(base, s) for s in range(steps)]
+    if c["kind"] == "reference":
+        # the first forward draws its seed on the host; the first optimizer.step() binds the
+        # fused Adam, which draws the clock's base seed next, and later steps read the clock
+        first = host_seed(1000)
+        torch.randint(0, 2 ** 62, (1,))
+        base = int(torch.randint(0, 2 ** 62, (1,)).item())
+        return [first] + [S.clock_seed(base, s) for s in range(1, steps)]
+    return [host_seed(1000 + s) for s in range(steps)]
+
+
+def _set_switches(monkeypatch, switches):
+    import ncf_amd.engine as E
+    for k, v in switches.items():
+        monkeypatch.setattr(E, k, v)
+
+
+def _check_form(name, eng, D, H, M, B):
+    """The predicate of the form that actually ran, as the A/B tests of test_gpu_parity assert
+    theirs."""
+    import ncf_amd.engine as E
+    sw, form = CASES[name]["sw"], CASES[name]["form"]
+    fused_one_launch = eng.attn_tower_step(D, H, M, HID)
+    if form in ("fused_small", "fused_80"):
+        assert fused_one_launch
+        assert eng._tiles(B) == ("" if form == "fused_80" else "_small")
+    elif form == "unfused":
+        assert not eng.attn_block(D, H, M) and not eng.mlp_fused(D, HID)
+        assert not eng.mlp_fused_wgrad() and not fused_one_launch
+    else:
+        assert form == "block"
+        assert eng.attn_block(D, H, M) and eng.mlp_fused(D, HID) and not fused_one_launch
+        assert eng.attn_rc(D, H, M) == sw.get("ATTN_RC", False)
+    assert E.TOWER_SPLIT is False
+    assert eng._tower_entry("ncf_mlp_fwd", True) == ("ncf_mlp_fwd" if "BF16_MM" in sw
+                                                      else "ncf_mlp_fwd_bf16")
+
+
+def _kjt(u, i):
+    return ncf.KeyedJaggedTensor.from_lengths_sync(
+        keys=["user_id", "product_id"], values=torch.cat([u, i]),
+        lengths=torch.ones(2 * u.numel(), dtype=torch.long)).to(DEV)
+
+
+def bf16_tables(sd):
+    """The state with its four embedding tables rounded to bf16 and widened again."""
+    out = dict(sd)
+    for K in TABLE_KEYS.values():
+        out[K] = sd[K].to(torch.bfloat16).float()
+    return out
+
+
+def gpu_run(name, monkeypatch, table_dtype=torch.float32):
+    """The case's steps on the GPU.  Returns (init state_dict on the CPU, batches, per-step
+    records with the step's seed, final state_dict)."""
+    from ncf_amd.trainer import FusedTrainStep
+    c = CASES[name]
+    D, H, M, B, p, steps, kind = (c[k] for k in ("D", "H", "M", "B", "p", "steps", "kind"))
+    _set_switches(monkeypatch, c["sw"])
+    m = make_model(D, H, M, p)
+    init = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    m = m.to(DEV)
+    eng = m.engine
+    batches = make_batches(B, M, steps, c["data_seed"])
+    step = opt = None
+    if kind == "reference":
+        opt = torch.optim.Adam(m.parameters(), lr=LR, weight_decay=WD)
+        m.train()
+    else:
+        step = FusedTrainStep(m, lr=LR, weight_decay=WD, deferred=kind == "clock",
+                              table_dtype=table_dtype)
+        assert (step.clock is not None) == (kind == "clock")
+        if table_dtype == torch.bfloat16:
+            # the reference starts from what the step object holds: the tables rounded to bf16
+            # (nearest even, as the CPU's cast) and widened; everything else untouched
+            held = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+            want = bf16_tables(init)
+            for k in init:
+                assert torch.equal(held[k], want[k]), k
+            assert all(v.dtype == torch.bfloat16 for v in step.tables_lp.values())
+            init = held
+    _check_form(name, eng, D, H, M, B)
+    rec = []
+    for s, (u, i, t) in enumerate(batches):
+        uniq = {"user": torch.unique(u), "item": torch.unique(i)}
+        # the step's seed: the device clock's when one is attached (FusedTrainStep's, or the one
+        # the fused Adam behind torch.optim.Adam binds at its first step()), else the host's draw
+        clock = step.clock if step is not None else eng.clock
+        assert (clock is not None) == (kind == "clock" or (kind == "reference" and s > 0))
+        seed = int(clock[1].item()) if clock is not None else host_seed(1000 + s)
+        if kind == "reference":
+            out = m(_kjt(u, i))
+            loss = torch.nn.functional.binary_cross_entropy(out, t.to(DEV))
+            opt.zero_grad()
+            loss.backward()
+            eng.materialize_table_grads()
+            grads = {n: q.grad.detach().cpu().clone() for n, q in m.named_parameters()
+                     if q.grad is not None}
+            tab = {k: grads.pop(K)[uniq[k.split("_")[1]]] for k, K in TABLE_KEYS.items()}
+            opt.step()
+            prob, loss = out.detach().cpu(), loss.detach().cpu()
+        else:
+            w = step(u.to(DEV), i.to(DEV), t.to(DEV))
+            torch.cuda.synchronize()
+            nu = dict(zip(("user", "item"), w.num_unique.cpu().tolist()))
+            assert torch.equal(w.uniq_u[:nu["user"]].cpu(), uniq["user"])
+            assert torch.equal(w.uniq_i[:nu["item"]].cpu(), uniq["item"])
+            prob, loss = w.prob.cpu().clone(), w.loss.cpu().clone()
+            grads = {n: eng.grad_view(n).cpu().clone() for n in eng.dense_names}
+            tab = {k: v[:nu[k.split("_")[1]]].cpu().clone() for k, v in w.G.items()}
+        rec.append(dict(seed=seed, prob=prob, loss=loss, grads=grads, tab=tab, uniq=uniq))
+    if step is not None:
+        step.sync()
+    final = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+    return init, batches, rec, final
+
+
+def compare(name, init, batches, rec, final, params=True):
+    """GPU records against the float64 oracle with the masks of each step's seed."""
+    c = CASES[name]
+    D, H, M, B, p = (c[k] for k in ("D", "H", "M", "B", "p"))
+    seeds = [r["seed"] for r in rec]
+    assert len(set(seeds)) == len(seeds)
+    if p == 0:      # (every keep-scale is 1: the dropout-off leg of the bf16-table cases)
+        assert all(float(x.min()) == 1.0 for x in S.step_masks(seeds[0], B, H, M, HID, p)["mlp"])
+    ora, ref = oracle_run(init, batches, seeds, H, M, p)
+    worst = dict(prob=0.0, loss=0.0, grad=0.0)
+    zones = {}
+    prev = None
+    for s, (g, o, (u, i, t)) in enumerate(zip(rec, ora, batches)):
+        masks = S.step_masks(g["seed"], B, H, M, HID, p)
+        # not vacuous: the masks drop about p of their elements, and differ from step to step
+        for x in ([masks["attn"]] + masks["mlp"]) if p > 0 else []:
+            keep = float((x > 0).mean())
+            assert abs(keep - (1 - p)) < 4 * (p * (1 - p) / x.size) ** 0.5, (s, x.shape, keep)
+        if prev is not None and p > 0:
+            assert not np.array_equal(prev["attn"], masks["attn"])
+            assert all(not np.array_equal(a, b) for a, b in zip(prev["mlp"], masks["mlp"]))
+        prev = masks
+        # no ReLU kink decides a comparison (margin: 4 x the measured fp32-vs-fp64 difference)
+        nearest = min(float(z.abs().min()) for z in o["pre"])
+        assert nearest > 4 * c["pre"], (s, nearest, c["pre"])
+        assert g["prob"].numel() == o["prob"].numel()
+        gprob = g["prob"].double().reshape(o["prob"].shape)
+        dp = (gprob - o["prob"]).abs().max().item()
+        dl = abs(float(g["loss"]) - float(o["loss"]))
+        worst["prob"], worst["loss"] = max(worst["prob"], dp), max(worst["loss"], dl)
+        print(f"{name} step {s}: |dprob| {dp:.3g} |dloss| {dl:.3g}")
+        assert dp < 5e-6, (s, dp)
+        assert dl < 5e-6, (s, dl)
+        dense = {k: v for k, v in o["grads"].items() if k not in TABLE_KEYS.values()}
+        assert set(g["grads"]) == set(dense), set(g["grads"]) ^ set(dense)
+        pairs = [(k, g["grads"][k], v) for k, v in dense.items()]
+        pairs += [(k, g["tab"][k], o["grads"][K][g["uniq"][k.split("_")[1]]])
+                  for k, K in TABLE_KEYS.items()]
+        for k, got, want in pairs:
+            got, want = got.double().numpy(), want.numpy()
+            frac = float((np.abs(got - want) / (2e-6 + 2e-4 * np.abs(want))).max())
+            worst["grad"] = max(worst["grad"], frac)
+            np.testing.assert_allclose(got, want, rtol=2e-4, atol=2e-6, err_msg=f"{name} step {s} {k}")
+        for k, v in o["grads"].items():
+            zones.setdefault(k, []).append(zone_from_grads(v.numpy(), o["before"][k].numpy(), WD))
+        if s == 0 and p > 0:
+            # the masks of another seed are another function: the comparison can tell
+            other = torch_masks(g["seed"] + 1, B, H, M, p)
+            po = O.forward(cast_state(init, torch.float64), u, i, training=True,
+                           negative_samples=M - 1, num_heads=H, temporal_dim=TDIM,
+                           n_layers=len(HID), dropout_masks=other)
+            assert (gprob - po).abs().max().item() > 1e-3
+    print(f"{name}: worst |dprob| {worst['prob']:.3g} |dloss| {worst['loss']:.3g} "
+          f"gradient at {worst['grad']:.3g} of its tolerance")
+    if params:
+        for k, zs in zones.items():
+            assert_params_close(k, final[k].numpy(), ref[k].numpy(), zs, LR, atol=5e-6)
+    return worst
+
+
+@pytest.mark.parametrize("name", [k for k in CASES if "table_dtype" not in CASES[k]])
+def test_train_step_with_dropout_vs_float64_oracle(monkeypatch, name):
+    init, batches, rec, final = gpu_run(name, monkeypatch)
+    compare(name, init, batches, rec, final)
+    # the seeds the CPU-side measurements were taken with (tests/test_dropout_stream.py)
+    assert [r["seed"] for r in rec] == case_seeds(name, len(rec))
+
+
+# ----------------------------------------------------------------------------- the stream itself
+@pytest.mark.parametrize("p", [0.2, 0.25, 0.5])
+@pytest.mark.parametrize("group,cols", [(1, 5), (1, 64), (1, 256), (16, 64), (16, 256)])
+def test_dropout_rows_scales_equal_restatement(p, group, cols):
+    """ncf_dropout_rows writes ncf_dropout_scale of index r * (cols / group) + c / group: bit
+    for bit the host restatement's, over seeds with a zero / non-zero high word and rows whose
+    index & 3 differs from row to row (cols = 5)."""
+    from ncf_amd import _lib
+    rows = 301
+    per = cols // group
+    x = torch.ones(rows, cols, device=DEV)
+    for seed in (0, 12345, 2 ** 62 - 1, (0x1234ABCD << 32) | 0x9E3779B9):
+        out = torch.empty(rows, cols, device=DEV)
+        sc = torch.empty(rows, per, device=DEV)
+        _lib.call("ncf_dropout_rows", x.data_ptr(), rows, cols, group, p, seed, out.data_ptr(),
+                  sc.data_ptr(), _lib.stream_ptr(DEV))
+        want = S.keep_scales(seed, rows * per, p).reshape(rows, per)
+        assert np.array_equal(sc.cpu().numpy().view(np.uint32), want.view(np.uint32)), seed
+        assert np.array_equal(out.cpu().numpy(), np.repeat(want, group, axis=1)), seed
+
+
+# ----------------------------------------------------------------------------- standalone MHA
+def _T(d):
+    return {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in d.items()}
+
+
+@pytest.mark.parametrize("tag,kind", [("mha5", None), ("mha50", None), ("mha5", "causal"),
+                                      ("mha5", "padding")])
+def test_mha_train_mode_vs_float64_oracle(f4, tag, kind):
+    """ncf.MultiHeadAttention(D, H, dropout=0.3).train() on the F4 inputs (attention.hip's LMAX 8
+    form for mha5, 64 for mha50), unmasked and with the causal / key-padding masks of
+    test_mha_mask_vs_oracle: y, dq, dk, dv and every weight gradient against O.mha in float64
+    with the restated keep-scales of the seed the call drew (ops.mha_forward), at that test's
+    tolerances.  Two calls draw fresh masks; eval ignores dropout."""
+    p = 0.3
+    Bn, L, D, H = [int(x) for x in f4[f"{tag}/shape"]]
+    w = _T(sub(f4, f"{tag}/w/"))
+    mod = ncf.MultiHeadAttention(D, H, dropout=p)
+    mod.load_state_dict(w)
+    mod = mod.to(DEV).train()
+    g = torch.Generator().manual_seed(3)
+    mask = None
+    if kind == "causal":
+        mask = torch.tril(torch.ones(L, L, dtype=torch.bool))
+    elif kind == "padding":
+        lens = torch.randint(1, L + 1, (Bn,), generator=g)
+        mask = (torch.arange(L)[None, :] < lens[:, None]).view(Bn, 1, 1, L)
+    qkv = [torch.from_numpy(f4[f"{tag}/{n}"]) for n in "qkv"]
+    gy = torch.from_numpy(f4[f"{tag}/gy"])
+    xs = [t.to(DEV).requires_grad_(True) for t in qkv]
+    seed = host_seed(77)
+    y = mod(*xs, mask=None if mask is None else mask.to(DEV))
+    y.backward(gy.to(DEV))
+    keep = S.keep_scales(seed, Bn * H * L * L, p).reshape(Bn, H, L, L)
+    frac = float((keep > 0).mean())
+    assert abs(frac - (1 - p)) < 4 * (p * (1 - p) / keep.size) ** 0.5, frac
+    ps = {f"a.{k}": v.double().requires_grad_(True) for k, v in w.items()}
+    rs = [t.double().requires_grad_(True) for t in qkv]
+    ry = O.mha(ps, "a.", *rs, H, drop_mask=torch.from_numpy(keep).double(), mask=mask)
+    ry.backward(gy.double())
+    print(f"mha {tag} {kind}: |dy| {(y.detach().cpu().double() - ry.detach()).abs().max().item():.3g}")
+    torch.testing.assert_close(y.detach().cpu().double(), ry.detach(), atol=2e-5, rtol=1e-5)
+    for a_, b_ in zip(xs, rs):
+        torch.testing.assert_close(a_.grad.cpu().double(), b_.grad, atol=2e-5, rtol=1e-4)
+    for n, q in mod.named_parameters():
+        torch.testing.assert_close(q.grad.cpu().double(), ps[f"a.{n}"].grad, atol=5e-5, rtol=1e-4)
+    # the masks of another seed: far outside the tolerance
+    with torch.no_grad():
+        other = O.mha({k: v.detach() for k, v in ps.items()}, "a.", *[t.detach() for t in rs], H,
+                      drop_mask=torch.from_numpy(
+                          S.keep_scales(seed + 1, Bn * H * L * L, p).reshape(Bn, H, L, L)).double(),
+                      mask=mask)
+        assert (y.detach().cpu().double() - other).abs().max().item() > 1e-3
+        # fresh masks per call; eval ignores dropout
+        margs = dict(mask=None if mask is None else mask.to(DEV))
+        y2, y3 = mod(*xs, **margs), mod(*xs, **margs)
+        assert not torch.equal(y2, y3)
+        mod.eval()
+        e1, e2 = mod(*xs, **margs), mod(*xs, **margs)
+        assert torch.equal(e1, e2)
+        plain = O.mha({k: v.detach() for k, v in ps.items()}, "a.", *[t.detach() for t in rs], H,
+                      mask=mask)
+        torch.testing.assert_close(e1.cpu().double(), plain, atol=2e-5, rtol=1e-5)
