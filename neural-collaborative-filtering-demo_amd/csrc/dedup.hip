@@ -90,26 +90,42 @@ __global__ __launch_bounds__(256) void k_keys_hist(
       if (h[p][d]) atomicAdd(&ghist[((int64_t)p * 2 + kind) * MAXR + d], h[p][d]);
 }
 
+// k_onesweep's LDS for a digit of `bits` bits (R = 2^bits), sized by the pass's radix so that a
+// sort tile can be resident on a CU beside a tower workgroup (ncf_common.h, NCF_TOWER_LDS):
+//   base[R] u32 | csum[256] u32 | s_tile u32 | wcnt[4][R] u16 | tcnt[R] u16
+// The per-wave and per-tile digit counts are at most TILE = 1024 keys: 16 bits hold them.
+constexpr size_t onesweep_lds(int bits) {
+  return ((size_t)4 + 4 * 2 + 2) * ((size_t)1 << bits) + 4 * 256 + 4;
+}
+static_assert(TILE <= 65535, "k_onesweep keeps its in-tile digit counts in 16 bits");
+static_assert(onesweep_lds(MAX_BITS) <= 36864,
+              "k_onesweep at the widest digit must fit the LDS a tower workgroup leaves free");
+static_assert(NCF_TOWER_LDS + onesweep_lds(MAX_BITS) <= NCF_CU_LDS,
+              "a sort tile must fit on a CU beside a tower workgroup");
+
 // One radix pass (digit = (key >> shift) & (R-1)) with decoupled look-back over tiles.
+// Dynamic LDS: onesweep_lds(bits) bytes.
 __global__ __launch_bounds__(256) void k_onesweep(
     const uint32_t* __restrict__ kin0, const uint32_t* __restrict__ vin0,
     const uint32_t* __restrict__ kin1, const uint32_t* __restrict__ vin1, int64_t n0, int64_t n1,
     int shift, int bits, const uint32_t* __restrict__ ghist, uint32_t* __restrict__ status,
     int nbmax, uint32_t* __restrict__ tickets, uint32_t* __restrict__ kout0,
     uint32_t* __restrict__ vout0, uint32_t* __restrict__ kout1, uint32_t* __restrict__ vout1) {
-  __shared__ uint32_t wcnt[4][MAXR];
-  __shared__ uint32_t tcnt[MAXR];
-  __shared__ uint32_t base[MAXR];
-  __shared__ uint32_t csum[256];
-  __shared__ uint32_t s_tile;
+  extern __shared__ uint32_t sweep_lds[];
+  const int R = 1 << bits;
+  uint32_t* const base = sweep_lds;                 // [R]
+  uint32_t* const csum = base + R;                  // [256]
+  uint32_t& s_tile = csum[256];
+  uint16_t* const wcnt0 = reinterpret_cast<uint16_t*>(csum + 257);   // [4][R]
+  uint16_t* const tcnt = wcnt0 + 4 * R;             // [R]
   const int kind = blockIdx.y;
   const int64_t n = kind ? n1 : n0;
   if (n == 0) return;
   const int nb = (int)((n + TILE - 1) / TILE);
-  const int R = 1 << bits;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  uint16_t* const wc = wcnt0 + w * R;               // this wave's counts
   if (tid == 0) s_tile = atomicAdd(&tickets[kind], 1u);
-  for (int i = tid; i < 4 * R; i += 256) wcnt[i / R][i % R] = 0;
+  for (int i = tid; i < 2 * R; i += 256) reinterpret_cast<uint32_t*>(wcnt0)[i] = 0;
   __syncthreads();
   const int tile = (int)s_tile;
   if (tile >= nb) return;
@@ -138,10 +154,10 @@ __global__ __launch_bounds__(256) void k_onesweep(
     }
     const uint32_t before = (uint32_t)__popcll(peers & lt);
     uint32_t c = 0;
-    if (ok[it]) c = wcnt[w][dig[it]];
+    if (ok[it]) c = wc[dig[it]];
     __builtin_amdgcn_wave_barrier();
     loc[it] = c + before;
-    if (ok[it] && before == 0) wcnt[w][dig[it]] = c + (uint32_t)__popcll(peers);
+    if (ok[it] && before == 0) wc[dig[it]] = (uint16_t)(c + (uint32_t)__popcll(peers));
     __builtin_amdgcn_wave_barrier();
   }
   __syncthreads();
@@ -150,11 +166,11 @@ __global__ __launch_bounds__(256) void k_onesweep(
     uint32_t run = 0;
 #pragma unroll
     for (int ww = 0; ww < 4; ++ww) {
-      const uint32_t c = wcnt[ww][d];
-      wcnt[ww][d] = run;
+      const uint32_t c = wcnt0[ww * R + d];
+      wcnt0[ww * R + d] = (uint16_t)run;
       run += c;
     }
-    tcnt[d] = run;
+    tcnt[d] = (uint16_t)run;
     st_status(&st[(int64_t)tile * R + d], (tile == 0 ? ST_INCL : ST_AGG) | run);
   }
   // global digit starts: exclusive scan of this pass's histogram (chunk per thread + LDS scan)
@@ -234,7 +250,7 @@ __global__ __launch_bounds__(256) void k_onesweep(
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     if (!ok[it]) continue;
-    const uint32_t pos = base[dig[it]] + wcnt[w][dig[it]] + loc[it];
+    const uint32_t pos = base[dig[it]] + wc[dig[it]] + loc[it];
     kout[pos] = key[it];
     vout[pos] = val[it];
   }
@@ -576,7 +592,8 @@ extern "C" int ncf_dedup_ids2(const int64_t* ids0, int64_t n0, int64_t rows0, co
   uint32_t *ko0 = w.kb0, *vo0 = w.vb0, *ko1 = w.kb1, *vo1 = w.vb1;
   const int64_t R = 1ll << bits;
   for (int p = 0; p < passes; ++p) {
-    hipLaunchKernelGGL(k_onesweep, dim3(w.nb, 2), dim3(256), 0, st, ki0, vi0, ki1, vi1, n0, n1,
+    hipLaunchKernelGGL(k_onesweep, dim3(w.nb, 2), dim3(256), onesweep_lds(bits), st, ki0, vi0, ki1,
+                       vi1, n0, n1,
                        p * bits, bits, w.ghist + (int64_t)p * 2 * MAXR,
                        w.status + (int64_t)p * 2 * w.nb * R, w.nb, w.tickets + 2 * p, ko0, vo0,
                        ko1, vo1);

@@ -1112,6 +1112,8 @@ __global__ __launch_bounds__(kThreads) void k_mlp_bwd(const float* __restrict__ 
 
 constexpr size_t kLds = sizeof(float) * (kRows * kPQ + kPSize);
 constexpr size_t kLdsFwd = sizeof(float) * 16 * kFwdRT * (kPQ + kPP);
+static_assert(kLds <= NCF_TOWER_LDS && kLdsFwd <= NCF_TOWER_LDS,
+              "the id sort is sized to the LDS a tower workgroup leaves free (ncf_common.h)");
 static_assert(kWaves * 3 * N0 <= kPSize, "ln_bwd scratch must fit in buffer P");
 static_assert(kWaves * Lay<128>::kHeadW <= kPSize, "head scratch must fit in buffer P");
 static_assert(kWaves * 3 * N1 <= kRows * kPQ, "ln_bwd scratch of layer 1 must fit in buffer Q");

@@ -12,6 +12,13 @@
 
 #define NCF_WAVE 64
 
+// LDS of one gfx950 CU, and the dynamic LDS a fused tower workgroup holds (mlp_tower_dev.h kLds;
+// tower_fused.hip kLdsFused / kLdsFusedBwd).  The tower kernels run one workgroup per CU, so
+// NCF_CU_LDS - NCF_TOWER_LDS = 38,400 B is what a kernel on another queue may use to be resident
+// beside one: the next batch's id sort is sized to it (dedup.hip asserts it).
+constexpr size_t NCF_CU_LDS = 160 * 1024;
+constexpr size_t NCF_TOWER_LDS = 125440;
+
 // ---------------------------------------------------------------- error handling (host)
 // Thread-local last-error string exposed through ncf_last_error().
 void ncf_set_error(const char* fmt, ...);

@@ -130,23 +130,51 @@ __global__ __launch_bounds__(256) void k_reduce_batch1(const BatchArgs a, float*
 
 // stage 2: one thread per output element (four per thread for a vec descriptor) of the
 // multi-chunk descriptors
+// k_reduce_parts' order: "wave" w sums rows w, w+4, ... — while four more of its rows remain
+// (p + 12 < pe), a group of four into accumulators 0..3; its last (at most three) rows into
+// accumulator 0 — then (a0 + a1) + (a2 + a3) per wave and (w0 + w1) + (w2 + w3).
+// Every load of a batch of kBatch rows (the float form 64, the float4 form 32: 128 registers) is
+// issued before the batch's first add: one round of memory latency per batch where the rolled
+// loops above waited for one per group of four rows, per wave (a dozen in series for the 25
+// chunk rows of the C2 step's embedding-LayerNorm gradients).  A batch is made of groups of 16
+// consecutive rows (row 16 g + 4 k + w: wave w, slot k); rows past pe load row pe - 1 again
+// (always valid) and are not added.  Each accumulator takes the same rows in the same
+// (ascending) order as before: the same bits.
 template <typename T>
 __device__ __forceinline__ T stage2_sum(const float* __restrict__ s, int64_t L, int pe) {
-  // k_reduce_parts' order: "wave" w sums rows w, w+4, ... with 4 accumulators, fixed combine
+  constexpr int kBatch = sizeof(T) == sizeof(float) ? 64 : 32;
+  T a[4][4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[w][k] = zero<T>();
+  for (int b = 0; b < pe; b += kBatch) {
+    T v[kBatch];
+#pragma unroll
+    for (int g = 0; g < kBatch; g += 16) {
+      if (b + g < pe) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          v[g + j] = *(const T*)(s + (int64_t)min(b + g + j, pe - 1) * L);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < kBatch; g += 16) {
+      if (b + g < pe) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int w = j & 3, k = j >> 2;
+          // wave w's group starting at row b + g + w is a full one iff its last row exists
+          const bool full = b + g + w + 12 < pe;
+          if (full) a[w][k] += v[g + j];
+          else if (b + g + j < pe) a[w][0] += v[g + j];
+        }
+      }
+    }
+  }
   T ws[4];
 #pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    T a0 = zero<T>(), a1 = zero<T>(), a2 = zero<T>(), a3 = zero<T>();
-    int p = w;
-    for (; p + 12 < pe; p += 16) {
-      a0 += *(const T*)(s + (int64_t)p * L);
-      a1 += *(const T*)(s + (int64_t)(p + 4) * L);
-      a2 += *(const T*)(s + (int64_t)(p + 8) * L);
-      a3 += *(const T*)(s + (int64_t)(p + 12) * L);
-    }
-    for (; p < pe; p += 4) a0 += *(const T*)(s + (int64_t)p * L);
-    ws[w] = (a0 + a1) + (a2 + a3);
-  }
+  for (int w = 0; w < 4; ++w) ws[w] = (a[w][0] + a[w][1]) + (a[w][2] + a[w][3]);
   return (ws[0] + ws[1]) + (ws[2] + ws[3]);
 }
 

@@ -88,6 +88,8 @@ __global__ __launch_bounds__(T::kThreads) void k_attn_mlp_bwd(
 
 constexpr size_t kLdsFused = T::kLdsFwd + (kAttnInQ ? 0 : sizeof(float) * kAttnFwdFloats);
 constexpr size_t kLdsFusedBwd = T::kLds;
+static_assert(kLdsFused <= NCF_TOWER_LDS && kLdsFusedBwd <= NCF_TOWER_LDS,
+              "the id sort is sized to the LDS a fused tower workgroup leaves free (ncf_common.h)");
 static_assert(sizeof(float) * (5 * kRp * A::AG<kD>::kPitch + kGW * 8 * kM * kM) <= kLdsFusedBwd,
               "the attention backward (8 heads at most) fits the tower backward's LDS");
 static_assert(kRp * A::AG<kD>::kPitch <= T::kRows * T::kPQ,

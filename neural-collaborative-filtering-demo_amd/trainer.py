@@ -42,7 +42,11 @@ GRAPH_HORIZON = 1 << 16
 # right after that kernel (engine.backward reduce_side), beside the embedding backward and the
 # table Adam; joined before the flat Adam close.  Same bits (the bitwise suite runs it).  Off:
 # measured slower (3 interleaved runs each: 0.3028 / 0.3033 against 0.2866 / 0.2888 ms/step —
-# the 105 MB of partials read beside the embedding backward and the apply slow both)
+# the 105 MB of partials read beside the embedding backward and the apply slow both).  Measured
+# again once the next batch's id sort fitted beside the tower and left the side queue free
+# early, with the late catch-up moved to the step's own stream behind the fused apply (DESIGN
+# §10): still slower, 0.2679-0.2714 against 0.2601-0.2620 ms/step — k_piece_reduce_ln 25 -> 35 us
+# beside the side-stream reductions, and the catch-up's 23 us joined the critical path
 EARLY_REDUCE = False
 # The deferred table Adam's apply of the step fused into the embedding backward
 # (ncf_embedding_bwd_reduce_apply_clock: a row steps where its gradient rows complete; the same
