@@ -40,6 +40,8 @@ def linear(x: Tensor, w: Tensor, b: Tensor) -> Tensor:
     return x @ w.t() + b
 
 
+_linear = linear    # (forward's ``linear=`` argument shadows the name)
+
 def mha(p: Dict[str, Tensor], pre: str, q_in: Tensor, k_in: Tensor, v_in: Tensor,
         num_heads: int, drop_mask: Optional[Tensor] = None,
         mask: Optional[Tensor] = None) -> Tensor:
@@ -77,8 +79,10 @@ def sinusoid_pe(max_period: int, dim: int) -> Tensor:
     return pe
 
 
-def mlp_tower(p: Dict[str, Tensor], x: Tensor, n_layers: int, masks=None) -> Tensor:
-    """self.mlp (architecture.py:230-242): n x [Linear, ReLU, LayerNorm, Dropout]."""
+def mlp_tower(p: Dict[str, Tensor], x: Tensor, n_layers: int, masks=None, linear=linear) -> Tensor:
+    """self.mlp (architecture.py:230-242): n x [Linear, ReLU, LayerNorm, Dropout].  ``linear``:
+    what the tower's Linears compute (default: this module's ``linear``; tests/bf16_tower.py
+    passes the bf16 tower's, with its operand rounding restated)."""
     for l in range(n_layers):
         x = torch.relu(linear(x, p[f"mlp.{4 * l}.weight"], p[f"mlp.{4 * l}.bias"]))
         x = layer_norm(x, p[f"mlp.{4 * l + 2}.weight"], p[f"mlp.{4 * l + 2}.bias"])
@@ -89,9 +93,11 @@ def mlp_tower(p: Dict[str, Tensor], x: Tensor, n_layers: int, masks=None) -> Ten
 
 def forward(p: Dict[str, Tensor], user_ids: Tensor, item_ids: Tensor, *, training: bool,
             negative_samples: int, num_heads: int, temporal_dim: int, n_layers: int,
-            dropout_masks=None) -> Tensor:
+            dropout_masks=None, linear=linear) -> Tensor:
     """AdvancedNCF.forward (architecture.py:258-381) on a KJT whose values are
-    [user_ids ‖ item_ids] with unit lengths.  Returns probabilities [N, 1]."""
+    [user_ids ‖ item_ids] with unit lengths.  Returns probabilities [N, 1].  ``linear`` replaces
+    the MLP tower's three Linears only (mlp_tower); every other Linear stays this module's."""
+    tower_linear, linear = linear, _linear
     n = user_ids.numel()
     M = 1 + negative_samples if training else 1                  # :275
     B = n // M                                                   # :276
@@ -109,7 +115,7 @@ def forward(p: Dict[str, Tensor], user_ids: Tensor, item_ids: Tensor, *, trainin
     att = mha(p, ATT, xu, xi, xi, num_heads, am).reshape(n, -1)  # :319-326
     comb = torch.cat([att, torch.zeros(n, temporal_dim)], 1)     # :329-340
     mm = None if dropout_masks is None else dropout_masks.get("mlp")
-    h = mlp_tower(p, comb, n_layers, mm)                         # :344
+    h = mlp_tower(p, comb, n_layers, mm, tower_linear)           # :344
     mlp_pred = linear(h, p["mlp_output.weight"], p["mlp_output.bias"])     # :345
     z = linear(torch.cat([mf_pred, mlp_pred], 1), p["final.0.weight"], p["final.0.bias"])
     return torch.sigmoid(z)                                      # :353-354
@@ -209,15 +215,17 @@ def used_param_names(names, n_layers):
 
 
 def train_step(p: Dict[str, Tensor], opt: AdamState, user_ids, item_ids, targets, *,
-               negative_samples, num_heads, temporal_dim, n_layers, dropout_masks=None):
+               negative_samples, num_heads, temporal_dim, n_layers, dropout_masks=None,
+               linear=linear):
     """One ModelTrainer.train_epoch batch (trainer.py:253-285): forward, BCE, zero_grad,
     backward (autograd on the CPU restatement), no clipping, Adam.step.
-    ``p`` holds leaf tensors and is updated in place.  Returns (prob, loss, grads)."""
+    ``p`` holds leaf tensors and is updated in place.  Returns (prob, loss, grads).
+    ``linear``: the MLP tower's Linears (see ``forward``)."""
     names = used_param_names(list(p.keys()), n_layers)
     leaves = {k: (v.detach().requires_grad_(True) if k in names else v) for k, v in p.items()}
     prob = forward(leaves, user_ids, item_ids, training=True, negative_samples=negative_samples,
                    num_heads=num_heads, temporal_dim=temporal_dim, n_layers=n_layers,
-                   dropout_masks=dropout_masks)
+                   dropout_masks=dropout_masks, linear=linear)
     loss = bce_loss(prob, targets)
     gl = torch.autograd.grad(loss, [leaves[k] for k in names])
     grads = dict(zip(names, gl))

@@ -93,6 +93,31 @@ CASES = {
                            table_dtype="bf16"),
 }
 
+# The bf16 tower (engine.BF16_MM at its default: the tower's Linears on bf16 MFMA), one
+# host-seeded step each; tests/test_gpu_bf16.py compares them with tests/bf16_tower.py's
+# restatement and holds their CPU-side measurements (no ``pre``: the layer-by-layer comparison
+# reads ReLU' from the step's own rows, and the end-to-end tolerances are measured flip noise).
+# lw_*: the tower's own launch with a and dlin stored (weight gradients by wgrad.hip), and the
+# same step with the weight gradients fused (*_fw).  e2e_*: the forms that keep everything in LDS.
+_LW = {"FUSE_ATTN_TOWER": False, "MLP_WGRAD": False}
+_LW_FW = {"FUSE_ATTN_TOWER": False, "MLP_WGRAD": True}
+
+
+def _mm(D, H, M, B, p, form, sw, data_seed):
+    return _case(D, H, M, B, p, 1, "host", form, sw, data_seed, None, table_dtype="bf16",
+                 tower="bf16")
+
+
+for _n, (_D, _H, _M, _B, _p) in {"d64_p0": (64, 4, 5, 37, 0.0), "d64_p02": (64, 4, 5, 37, 0.2),
+                                  "d128_p0": (128, 8, 6, 19, 0.0), "d128_p02": (128, 8, 6, 19, 0.2),
+                                  "b1_p02": (64, 4, 5, 1, 0.2)}.items():
+    CASES["bf16mm_lw_" + _n] = _mm(_D, _H, _M, _B, _p, "block", _LW, 1)
+    CASES["bf16mm_lw_" + _n + "_fw"] = _mm(_D, _H, _M, _B, _p, "block", _LW_FW, 1)
+# (data seeds picked on the CPU: tests/test_gpu_bf16.py E2E)
+CASES["bf16mm_e2e_small"] = _mm(64, 4, 5, 37, 0.2, "fused_small", {}, 3)
+CASES["bf16mm_e2e_80"] = _mm(64, 4, 5, 37, 0.2, "fused_80", {"SMALL_TILE_GROUPS": 0}, 8)
+CASES["bf16mm_e2e_d128"] = _mm(128, 8, 6, 19, 0.2, "block", {}, 5)
+
 
 def make_model(D, H, M, p):
     torch.manual_seed(INIT_SEED)
@@ -150,10 +175,11 @@ def tower_preacts(p, u, i, M, H, masks):
     return out
 
 
-def oracle_run(init, batches, seeds, H, M, p, dtype=torch.float64):
+def oracle_run(init, batches, seeds, H, M, p, dtype=torch.float64, linear=O.linear):
     """The oracle's trajectory over ``batches`` with the masks of ``seeds`` (one per step), on
     one host thread (test_gpu_fullsize: torch's threaded CPU reductions do not fix their order).
-    Per step: prob, loss, grads, the parameters before the step, the pre-activations."""
+    Per step: prob, loss, grads, the parameters before the step, the pre-activations.
+    ``linear``: the tower's Linears (tests/bf16_tower.py restates the bf16 tower's)."""
     threads = torch.get_num_threads()
     torch.set_num_threads(1)
     try:
@@ -167,7 +193,7 @@ def oracle_run(init, batches, seeds, H, M, p, dtype=torch.float64):
                 pre = tower_preacts(ref, u, i, M, H, masks)
             prob, loss, grads = O.train_step(ref, opt, u, i, t.to(dtype), negative_samples=M - 1,
                                              num_heads=H, temporal_dim=TDIM, n_layers=len(HID),
-                                             dropout_masks=masks)
+                                             dropout_masks=masks, linear=linear)
             rec.append(dict(prob=prob, loss=loss, grads=grads, before=before, pre=pre))
         return rec, ref
     finally:
@@ -234,9 +260,14 @@ def bf16_tables(sd):
     return out
 
 
-def gpu_run(name, monkeypatch, table_dtype=torch.float32):
+TOWER_KEYS = ("y", "mf_pred", "r", "a", "mean", "rstd", "dlin", "dy", "mlp_pred", "prob")
+
+
+def gpu_run(name, monkeypatch, table_dtype=torch.float32, tower=False):
     """The case's steps on the GPU.  Returns (init state_dict on the CPU, batches, per-step
-    records with the step's seed, final state_dict)."""
+    records with the step's seed, final state_dict).  ``tower``: each record also carries the
+    tower's tensors of the step's workspace (TOWER_KEYS; what the form that ran does not store
+    is stale or uninitialised there) for tests/bf16_tower.py's layer-by-layer comparison."""
     from ncf_amd.trainer import FusedTrainStep
     c = CASES[name]
     D, H, M, B, p, steps, kind = (c[k] for k in ("D", "H", "M", "B", "p", "steps", "kind"))
@@ -293,6 +324,12 @@ def gpu_run(name, monkeypatch, table_dtype=torch.float32):
             grads = {n: eng.grad_view(n).cpu().clone() for n in eng.dense_names}
             tab = {k: v[:nu[k.split("_")[1]]].cpu().clone() for k, v in w.G.items()}
         rec.append(dict(seed=seed, prob=prob, loss=loss, grads=grads, tab=tab, uniq=uniq))
+        if tower:
+            assert step is not None     # (the fused step hands its workspace back)
+            tw = {k: getattr(w, k) for k in TOWER_KEYS}
+            rec[-1]["tower"] = {k: [x.cpu().clone() for x in v] if isinstance(v, list)
+                                else v.cpu().clone() for k, v in tw.items()}
+            rec[-1]["tower"]["grads"] = grads
     if step is not None:
         step.sync()
     final = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
