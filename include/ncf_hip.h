@@ -246,6 +246,24 @@ int ncf_attention_bwd(const float* q, const float* k, const float* v, const floa
                       int64_t dim, float dropout_p, uint64_t seed, const ncf_step_clock* clock,
                       float* grad_scores, float* grad_q, float* grad_k, float* grad_v,
                       void* stream);
+/* The core with a key/value length of its own (architecture.py:39-41 view q, k and v each with
+ * .view(batch, -1, H, hd); :210-214 sequence_attention: one query over a user's history).
+ * q, out, grad_q: [groups*len_q, dim]; k, v, grad_k, grad_v: [groups*len_k, dim]; probs
+ * (pre-dropout softmax, saved for the backward) and mask (bytes, 0 = masked, NULL = none):
+ * [groups, heads, len_q, len_k].  1 <= len_q, len_k <= 64, head dim in {8,16,32,64}.  One wave per
+ * (group, head), K and V staged in LDS; the backward is one launch, without a grad_scores
+ * buffer and without atomics (bitwise reproducible).  Dropout element ((b*heads + h)*len_q + i)
+ * *len_k + j of the stream ncf_attention_fwd draws from (its own index at len_q == len_k), seed
+ * + (clock ? clock->seed : 0).  A fully masked row is NaN, as in ncf_attention_fwd_masked.    */
+int ncf_attention_x_fwd(const float* q, const float* k, const float* v, int64_t groups,
+                        int64_t len_q, int64_t len_k, int64_t heads, int64_t dim,
+                        float dropout_p, uint64_t seed, const ncf_step_clock* clock,
+                        const uint8_t* mask, float* probs, float* out, void* stream);
+int ncf_attention_x_bwd(const float* q, const float* k, const float* v, const float* probs,
+                        const float* grad_out, int64_t groups, int64_t len_q, int64_t len_k,
+                        int64_t heads, int64_t dim, float dropout_p, uint64_t seed,
+                        const ncf_step_clock* clock, float* grad_q, float* grad_k, float* grad_v,
+                        void* stream);
 /* The whole a5 block in one launch per direction (D = 64 or 128, M <= 6; ncf_attn_block_supported):
  * forward  q,k,v = LN rows x W^T + b, the core above (same P layout and dropout stream), y =
  *          o Wo^T + bo.  q = k = NULL: nothing is stashed (with M == 1 and no dropout this is

@@ -23,6 +23,11 @@ class NCFLibraryError(RuntimeError):
     pass
 
 
+class NCFArgumentError(NCFLibraryError, ValueError):
+    """An entry point returned NCF_ERR_ARG (a shape or pointer it refuses, before any launch): a
+    ValueError, as check() has always raised for it, that is also the library's own error."""
+
+
 P = ctypes.c_void_p
 I64 = ctypes.c_int64
 I32 = ctypes.c_int
@@ -71,6 +76,8 @@ SIGNATURES = {
     "ncf_attention_fwd": (I32, [P, P, P, I64, I64, I64, I64, F32, U64, P, P, P, P]),
     "ncf_attention_fwd_masked": (I32, [P, P, P, I64, I64, I64, I64, F32, U64, P, P, P, P, P]),
     "ncf_attention_bwd": (I32, [P, P, P, P, P, I64, I64, I64, I64, F32, U64, P, P, P, P, P, P]),
+    "ncf_attention_x_fwd": (I32, [P, P, P, I64, I64, I64, I64, I64, F32, U64, P, P, P, P, P]),
+    "ncf_attention_x_bwd": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, F32, U64, P, P, P, P, P]),
     "ncf_attn_block_supported": (I32, [I64, I64, I64]),
     "ncf_mlp_fused_supported": (I32, [I64, I64, P]),
     "ncf_attn_mlp_fused_supported": (I32, [I64, I64, I64, I64, P]),
@@ -359,7 +366,7 @@ def check(rc: int, name: str):
     if rc != 0:
         msg = _lib.ncf_last_error().decode(errors="replace") if _lib is not None else ""
         if rc == -1:
-            raise ValueError(f"{name}: {msg}")
+            raise NCFArgumentError(f"{name}: {msg}")
         raise RuntimeError(f"{name} failed ({rc}): {msg}")
 
 

@@ -25,8 +25,11 @@ log = logging.getLogger(__name__)
 
 class MultiHeadAttention(nn.Module):
     """Parameter container with the reference's names (:18-33).  Inside AdvancedNCF its math
-    runs in the fused engine; standalone use (CategoryHierarchy with L = 1) goes through
-    ``attend_single_key``."""
+    runs in the fused engine; a plain module call (``ops.mha_forward``, with autograd) takes a
+    query of length L_q and key/value of length L_k, each 1..64 and equal or not, a 2-D [B, D]
+    input counting as length 1 (``sequence_attention(user_row, history, history)`` returns
+    [B, 1, D]), head dim 8 / 16 / 32 / 64 and the reference's optional mask; CategoryHierarchy
+    (L = 1) goes through ``attend_single_key``."""
 
     def __init__(self, embed_dim: int, num_heads: int = 4, dropout: float = 0.1):
         super().__init__()

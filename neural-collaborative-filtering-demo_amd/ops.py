@@ -1,9 +1,11 @@
 """Standalone HIP ops for the modules that also exist outside the fused AdvancedNCF step:
-MultiHeadAttention (any group length <= 64), TemporalEncoding and CategoryHierarchy.
+MultiHeadAttention (query length and key/value length each 1..64, equal or not; head dim 8, 16,
+32 or 64), TemporalEncoding and CategoryHierarchy.
 
 They mirror the reference modules' forward semantics (src/model/architecture.py:35-57, :86-94,
-:111-119) and run on the same kernels as the engine (MFMA projections + attention core), with
-autograd support for MultiHeadAttention and TemporalEncoding.  GPU only.
+:111-119) and run on the same kernels as the engine (MFMA projections + attention core;
+attention_x.hip's core when the key/value length differs from the query's), with autograd
+support for MultiHeadAttention and TemporalEncoding.  GPU only.
 """
 import torch
 
@@ -33,46 +35,56 @@ def _wgrad(dY, X, dW, n, m_out, k_in, dbias=None):
 class _MHAFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, drop_p, seed, mask, q_in, k_in, v_in, wq, bq, wk, bk, wv, bv, wo, bo):
-        Bn, L, D = q_in.shape
+        Bn, Lq, D = q_in.shape
+        Lk = k_in.shape[1]
         H = mod.num_heads
-        n = Bn * L
+        nq, nk = Bn * Lq, Bn * Lk
         dev = q_in.device
-        xq, xk, xv = (t.reshape(n, D).contiguous().float() for t in (q_in, k_in, v_in))
-        q, k, v, o, y = (torch.empty(n, D, device=dev) for _ in range(5))
-        P = torch.empty(Bn * H * L * L, device=dev)
-        _gemm(xq, D, 0, wq, D, 1, q, D, n, D, D, bq)
-        _gemm(xk, D, 0, wk, D, 1, k, D, n, D, D, bk)
-        _gemm(xv, D, 0, wv, D, 1, v, D, n, D, D, bv)
-        if mask is None:
-            _lib.call("ncf_attention_fwd", ptr(q), ptr(k), ptr(v), Bn, L, H, D, drop_p, seed, None,
+        xq, xk, xv = (t.reshape(-1, D).contiguous().float() for t in (q_in, k_in, v_in))
+        q, o, y = (torch.empty(nq, D, device=dev) for _ in range(3))
+        k, v = (torch.empty(nk, D, device=dev) for _ in range(2))
+        P = torch.empty(Bn * H * Lq * Lk, device=dev)
+        _gemm(xq, D, 0, wq, D, 1, q, D, nq, D, D, bq)
+        _gemm(xk, D, 0, wk, D, 1, k, D, nk, D, D, bk)
+        _gemm(xv, D, 0, wv, D, 1, v, D, nk, D, D, bv)
+        if Lq != Lk:    # attention_x.hip; mask [Bn, H, Lq, Lk] bytes or NULL
+            _lib.call("ncf_attention_x_fwd", ptr(q), ptr(k), ptr(v), Bn, Lq, Lk, H, D, drop_p, seed,
+                      None, ptr(mask), ptr(P), ptr(o), _lib.stream_ptr(dev))
+        elif mask is None:
+            _lib.call("ncf_attention_fwd", ptr(q), ptr(k), ptr(v), Bn, Lq, H, D, drop_p, seed, None,
                       ptr(P), ptr(o), _lib.stream_ptr(dev))
         else:    # [Bn, H, L, L] bytes, 0 = masked (architecture.py:47-48)
-            _lib.call("ncf_attention_fwd_masked", ptr(q), ptr(k), ptr(v), Bn, L, H, D, drop_p, seed,
+            _lib.call("ncf_attention_fwd_masked", ptr(q), ptr(k), ptr(v), Bn, Lq, H, D, drop_p, seed,
                       None, ptr(mask), ptr(P), ptr(o), _lib.stream_ptr(dev))
-        _gemm(o, D, 0, wo, D, 1, y, D, n, D, D, bo)
+        _gemm(o, D, 0, wo, D, 1, y, D, nq, D, D, bo)
         ctx.save_for_backward(xq, xk, xv, q, k, v, P, o, wq, wk, wv, wo)
-        ctx.meta = (Bn, L, D, H, drop_p, seed)
-        return y.view(Bn, L, D)
+        ctx.meta = (Bn, Lq, Lk, D, H, drop_p, seed)
+        return y.view(Bn, Lq, D)
 
     @staticmethod
     def backward(ctx, gy):
         xq, xk, xv, q, k, v, P, o, wq, wk, wv, wo = ctx.saved_tensors
-        Bn, L, D, H, drop_p, seed = ctx.meta
-        n = Bn * L
+        Bn, Lq, Lk, D, H, drop_p, seed = ctx.meta
+        nq, nk = Bn * Lq, Bn * Lk
         dev = gy.device
-        dy = gy.reshape(n, D).contiguous().float()
+        dy = gy.reshape(nq, D).contiguous().float()
         g = {nm: torch.empty(D, D, device=dev) for nm in ("wq", "wk", "wv", "wo")}
         gb = {nm: torch.empty(D, device=dev) for nm in ("bq", "bk", "bv", "bo")}
-        _wgrad(dy, o, g["wo"], n, D, D, gb["bo"])
-        do = torch.empty(n, D, device=dev)
-        _gemm(dy, D, 0, wo, D, 0, do, D, n, D, D)
-        dS = torch.empty(Bn * H * L * L, device=dev)
-        dq, dk, dv = (torch.empty(n, D, device=dev) for _ in range(3))
-        _lib.call("ncf_attention_bwd", ptr(q), ptr(k), ptr(v), ptr(P), ptr(do), Bn, L, H, D,
-                  drop_p, seed, None, ptr(dS), ptr(dq), ptr(dk), ptr(dv), _lib.stream_ptr(dev))
+        _wgrad(dy, o, g["wo"], nq, D, D, gb["bo"])
+        do = torch.empty(nq, D, device=dev)
+        _gemm(dy, D, 0, wo, D, 0, do, D, nq, D, D)
+        dq = torch.empty(nq, D, device=dev)
+        dk, dv = (torch.empty(nk, D, device=dev) for _ in range(2))
+        if Lq != Lk:
+            _lib.call("ncf_attention_x_bwd", ptr(q), ptr(k), ptr(v), ptr(P), ptr(do), Bn, Lq, Lk, H,
+                      D, drop_p, seed, None, ptr(dq), ptr(dk), ptr(dv), _lib.stream_ptr(dev))
+        else:
+            dS = torch.empty(Bn * H * Lq * Lk, device=dev)
+            _lib.call("ncf_attention_bwd", ptr(q), ptr(k), ptr(v), ptr(P), ptr(do), Bn, Lq, H, D,
+                      drop_p, seed, None, ptr(dS), ptr(dq), ptr(dk), ptr(dv), _lib.stream_ptr(dev))
         outs = []
-        for dX, X, W, wn, bn in ((dq, xq, wq, "wq", "bq"), (dk, xk, wk, "wk", "bk"),
-                                 (dv, xv, wv, "wv", "bv")):
+        for dX, X, W, wn, bn, n, L in ((dq, xq, wq, "wq", "bq", nq, Lq), (dk, xk, wk, "wk", "bk", nk, Lk),
+                                       (dv, xv, wv, "wv", "bv", nk, Lk)):
             _wgrad(dX, X, g[wn], n, D, D, gb[bn])
             gx = torch.empty(n, D, device=dev)
             _gemm(dX, D, 0, W, D, 0, gx, D, n, D, D)
@@ -82,29 +94,39 @@ class _MHAFunction(torch.autograd.Function):
 
 
 def mha_forward(mod, query, key, value, mask=None):
-    """MultiHeadAttention.forward (architecture.py:35-57): query/key/value [B, L, D] (a 2-D
-    [B, D] input is a length-1 sequence, as the reference's .view(batch, -1, H, hd) makes it).
-    ``mask`` (:36, :47-48): any tensor that broadcasts against the scores [B, H, L, L]; where it
-    is 0 the score is -inf before the softmax (ncf_attention_fwd_masked)."""
+    """MultiHeadAttention.forward (architecture.py:35-57): query [B, L_q, D], key and value
+    [B, L_k, D], 1 <= L_q, L_k <= 64; each of them given 2-D [B, D] is a length-1 sequence, as the
+    reference's .view(batch, -1, H, hd) makes it (a 2-D query over a 3-D history is the
+    sequence_attention call, :210-214).  Returns [B, L_q, D].  ``mask`` (:36, :47-48): any tensor
+    that broadcasts against the scores [B, H, L_q, L_k]; where it is 0 the score is -inf before
+    the softmax.  L_k == L_q runs the training step's core (ncf_attention_fwd / _fwd_masked /
+    _bwd), any other pair of lengths ncf_attention_x_fwd / _x_bwd."""
     _require_cuda(query)
-    squeeze = query.dim() == 2
-    if squeeze:
-        query, key, value = query.unsqueeze(1), key.unsqueeze(1), value.unsqueeze(1)
-    if key.shape[1] != query.shape[1] or value.shape[1] != key.shape[1]:
-        raise NotImplementedError("MultiHeadAttention: key/value length must equal the query's "
-                                  "on this path (every reference call site passes equal lengths)")
+    for name, t in (("query", query), ("key", key), ("value", value)):
+        if t.dim() not in (2, 3):
+            raise ValueError(f"MultiHeadAttention: {name} must be [B, L, D] or [B, D], got "
+                             f"{tuple(t.shape)}")
+    query, key, value = (t.unsqueeze(1) if t.dim() == 2 else t for t in (query, key, value))
+    Bn, Lq, D = query.shape
+    for name, t in (("key", key), ("value", value)):
+        if t.shape[0] != Bn or t.shape[2] != D:
+            raise ValueError(f"MultiHeadAttention: {name} {tuple(t.shape)} does not match the "
+                             f"query's batch and embedding dimension {(Bn, D)}")
+    Lk = key.shape[1]
+    if value.shape[1] != Lk:     # the reference's matmul(attn_weights, v) fails the same way
+        raise RuntimeError(f"MultiHeadAttention: value length {value.shape[1]} differs from the "
+                           f"key length {Lk}")
     drop_p = float(mod.dropout.p) if mod.training else 0.0
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0 else 0
     m8 = None
     if mask is not None:
-        Bn, L = query.shape[0], query.shape[1]
         m = torch.as_tensor(mask, device=query.device)
-        # masked_fill(mask == 0, .) broadcasts the mask against the scores [B, H, L, L]
-        m8 = torch.broadcast_to(m != 0, (Bn, mod.num_heads, L, L)).to(torch.uint8).contiguous()
+        # masked_fill(mask == 0, .) broadcasts the mask against the scores [B, H, L_q, L_k]
+        m8 = torch.broadcast_to(m != 0, (Bn, mod.num_heads, Lq, Lk)).to(torch.uint8).contiguous()
     y = _MHAFunction.apply(mod, drop_p, seed, m8, query, key, value, mod.q_proj.weight, mod.q_proj.bias,
                            mod.k_proj.weight, mod.k_proj.bias, mod.v_proj.weight, mod.v_proj.bias,
                            mod.out_proj.weight, mod.out_proj.bias)
-    return y  # a 2-D input comes back [B, 1, D], as the reference's .view(batch, -1, D) makes it
+    return y  # a 2-D query comes back [B, 1, D], as the reference's .view(batch, -1, D) makes it
 
 
 class _TemporalFunction(torch.autograd.Function):
