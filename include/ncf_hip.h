@@ -720,6 +720,35 @@ int ncf_score_select(const int32_t* user_list, int64_t n_users, const uint32_t* 
                      const ncf_score_cand* cand, int64_t cap, int K,
                      float* out_score, int64_t* out_item, float* thr, uint32_t* overflow,
                      void* stream);
+/* The two selects leaving out the items each user has already seen.  user_ids: the ids the
+ * queries were built from, indexed like them; seen_offsets [num_users + 1] / seen_items: every
+ * user's seen items as a CSR over the whole user table, global item ids sorted ascending and
+ * unique within a user; item_ids (may be NULL): the global id of each index position, for an
+ * index over a subset of the catalogue.  A candidate whose global id is in its user's list is
+ * dropped before the re-scoring window, the K-th, the thr_check test and the overflow threshold
+ * are derived, so all of them are of the remaining candidates; a user id outside [0, num_users)
+ * has no list.  Fewer than K remaining: the trailing slots are (0, -1), and with thr_check the
+ * user is flagged 2; so is a user whose list overflowed with fewer than K of the cap records
+ * remaining (thr is then left as it was; otherwise an overflow returns the K-th remaining logit
+ * in thr, flag 1, as ncf_score_select does).  thr_check here may be any threshold the collect ran at or below: it makes
+ * the result provably the top K of the unseen items (the collect's own threshold bounds the K-th
+ * logit of the whole catalogue only). */
+int ncf_score_select_excl(const int32_t* user_list, int64_t n_users, const uint32_t* count,
+                          const ncf_score_cand* cand, int64_t cap, int K, float* out_score,
+                          int64_t* out_item, float* thr, uint32_t* overflow,
+                          const float* thr_check, const int64_t* user_ids, int64_t num_users,
+                          const int64_t* seen_offsets, const int32_t* seen_items,
+                          const int64_t* item_ids, void* stream);
+int ncf_score_select_rescored_excl(const int32_t* user_list, int64_t n_users,
+                                   const uint32_t* count, const ncf_score_cand* cand,
+                                   int64_t cap, int K, const float* queries, const float* items,
+                                   const float* item_bias, int64_t dim,
+                                   const uint32_t* item_norm_max, float c, float* out_score,
+                                   int64_t* out_item, float* thr, uint32_t* overflow,
+                                   const float* thr_check, const int64_t* user_ids,
+                                   int64_t num_users, const int64_t* seen_offsets,
+                                   const int32_t* seen_items, const int64_t* item_ids,
+                                   void* stream);
 /* Item-sharded scoring: merge per-user lists of L = W*K (score, global item id)
  * gathered from W item shards into the top-K by (score desc, item id asc); id < 0 = empty slot
  * (an empty output slot is (0, -1)).  L, K <= 8192; item ids < 2^32 - 1. */

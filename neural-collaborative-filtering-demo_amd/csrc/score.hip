@@ -28,6 +28,8 @@
 //                             and the host re-runs 3-4 for those users.  With a rank-j threshold
 //                             (j < K, a smaller sample: thr_check) it also checks that the K chosen
 //                             are provably the top K, and flags the user for a re-run if not.
+//                             ncf_score_select*_excl: the same without the candidates in the user's
+//                             list of seen items (k_select<.., EX>), always with thr_check.
 // Tilings: see k_collect (fp32) and k_collect3 (split bf16) below.
 #include "ncf_common.h"
 #include <algorithm>
@@ -1201,7 +1203,11 @@ __global__ __launch_bounds__(256) void k_sample16t(const float* __restrict__ q, 
   }
 }
 
-template <bool RS>
+// EX: the candidates whose global item id (item_ids[item], or the item itself) is in the user's
+// sorted list seen_items[seen_offsets[id] .. seen_offsets[id + 1]), id = user_ids[u], are made
+// non-members before anything is derived from the keys: the re-scoring window, the K-th key, the
+// check against thr_check and the threshold returned on overflow are all of the remaining ones.
+template <bool RS, bool EX = false>
 __global__ __launch_bounds__(256) void k_select(const int32_t* __restrict__ user_list,
                                                 int64_t n_users, const uint32_t* __restrict__ count,
                                                 const ncf_score_cand* __restrict__ cand,
@@ -1214,7 +1220,12 @@ __global__ __launch_bounds__(256) void k_select(const int32_t* __restrict__ user
                                                 int64_t* __restrict__ out_item,
                                                 float* __restrict__ thr_out,
                                                 uint32_t* __restrict__ overflow,
-                                                const float* __restrict__ thr_check) {
+                                                const float* __restrict__ thr_check,
+                                                const int64_t* __restrict__ user_ids,
+                                                int64_t num_users,
+                                                const int64_t* __restrict__ seen_offsets,
+                                                const int32_t* __restrict__ seen_items,
+                                                const int64_t* __restrict__ item_ids) {
   extern __shared__ unsigned long long sel[];   // [n2K] selected keys, then uint32 keys[cap]
   uint32_t* keys = reinterpret_cast<uint32_t*>(sel + n2K);
   __shared__ uint32_t hist[256];
@@ -1295,6 +1306,24 @@ __global__ __launch_bounds__(256) void k_select(const int32_t* __restrict__ user
   };
   if (tid == 0) s_n = 0;
   for (int j = tid; j < nc; j += 256) keys[j] = fkey(cc[j].logit);
+  if constexpr (EX) {
+    // (an id out of range was flagged by k_queries and raises on the host: no list is read)
+    const int64_t id = user_ids[u];
+    int64_t b = 0, e = 0;
+    if (id >= 0 && id < num_users) { b = seen_offsets[id]; e = seen_offsets[id + 1]; }
+    if (e > b) {
+      for (int j = tid; j < nc; j += 256) {
+        const int64_t it = cc[j].item;
+        const int64_t g = item_ids ? item_ids[it] : it;
+        int64_t l = b, h = e;   // lower bound of g in the user's sorted list
+        while (l < h) {
+          const int64_t mid = (l + h) >> 1;
+          if ((int64_t)seen_items[mid] < g) l = mid + 1; else h = mid;
+        }
+        if (l < e && (int64_t)seen_items[l] == g) keys[j] = 0;
+      }
+    }
+  }
   __syncthreads();
   uint32_t kmin, kmax, nmem;
   key_range(kmin, kmax, nmem);
@@ -1316,6 +1345,7 @@ __global__ __launch_bounds__(256) void k_select(const int32_t* __restrict__ user
     }
     for (int j = tid; j < nc; j += 256) {
       const ncf_score_cand rc = cc[j];
+      if constexpr (EX) { if (keys[j] == 0) continue; }
       if (rc.logit < lo) { keys[j] = 0; continue; }
       const int64_t it = rc.item;
       const float* pr = items + it * 64;
@@ -1375,9 +1405,14 @@ __global__ __launch_bounds__(256) void k_select(const int32_t* __restrict__ user
     // from the sample's K-th, a guaranteed bound)
     const bool under = !over && thr_check &&
         (ns < K || fkey_inv((uint32_t)(sel[K - 1] >> 32)) < thr_check[u]);
-    overflow[slot] = over ? 1u : (under ? 2u : 0u);
-    // a valid higher threshold for a re-run: the K-th best of the candidates seen
-    if (over && thr_out) thr_out[u] = fkey_inv((uint32_t)(sel[K - 1] >> 32));
+    // (EX: an overflowed list with fewer than K candidates left bounds nothing: flag 2 as well,
+    // the threshold left as it is; the host's re-run keeps cap >= K + the longest list, where K
+    // always remain)
+    const bool lost = EX && over && ns < K;
+    overflow[slot] = over ? (lost ? 2u : 1u) : (under ? 2u : 0u);
+    // a valid higher threshold for a re-run: the K-th best of the candidates seen (EX: of those
+    // not excluded)
+    if (over && thr_out && !lost) thr_out[u] = fkey_inv((uint32_t)(sel[K - 1] >> 32));
   }
 }
 
@@ -1715,6 +1750,32 @@ extern "C" int ncf_score_collect_split(const float* queries, const int32_t* user
   return NCF_OK;
 }
 
+// launch of k_select<RS, EX> (the arguments checked by the entry points below)
+template <bool RS, bool EX>
+static void select_launch(const int32_t* user_list, int64_t n_users, const uint32_t* count,
+                          const ncf_score_cand* cand, int64_t cap, int K, const float* queries,
+                          const float* items, const float* item_bias,
+                          const uint32_t* item_norm_max, float c, float* out_score,
+                          int64_t* out_item, float* thr, uint32_t* overflow,
+                          const float* thr_check, const int64_t* user_ids, int64_t num_users,
+                          const int64_t* seen_offsets, const int32_t* seen_items,
+                          const int64_t* item_ids, void* stream) {
+  int n2K = 1;
+  while (n2K < K) n2K <<= 1;
+  const size_t lds = sizeof(unsigned long long) * (size_t)n2K + sizeof(uint32_t) * (size_t)cap;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)k_select<RS, EX>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)((sizeof(unsigned long long) + sizeof(uint32_t)) * kSelectMax));
+    attr = true;
+  }
+  hipLaunchKernelGGL((k_select<RS, EX>), dim3((unsigned)n_users), dim3(256), lds,
+                     (hipStream_t)stream, user_list, n_users, count, cand, cap, K, n2K, queries,
+                     items, item_bias, item_norm_max, c, out_score, out_item, thr, overflow,
+                     thr_check, user_ids, num_users, seen_offsets, seen_items, item_ids);
+}
+
 extern "C" int ncf_score_select(const int32_t* user_list, int64_t n_users, const uint32_t* count,
                                 const ncf_score_cand* cand, int64_t cap,
                                 int K, float* out_score, int64_t* out_item, float* thr,
@@ -1722,18 +1783,9 @@ extern "C" int ncf_score_select(const int32_t* user_list, int64_t n_users, const
   NCF_CHECK_ARG(n_users >= 0 && K >= 1 && cap >= K && cap <= kSelectMax,
                 "ncf_score_select: need 1 <= K <= cap <= %d", kSelectMax);
   if (n_users == 0) return NCF_OK;
-  int n2K = 1;
-  while (n2K < K) n2K <<= 1;
-  const size_t lds = sizeof(unsigned long long) * (size_t)n2K + sizeof(uint32_t) * (size_t)cap;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_select<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((sizeof(unsigned long long) + sizeof(uint32_t)) * kSelectMax));
-    attr = true;
-  }
-  hipLaunchKernelGGL(k_select<false>, dim3((unsigned)n_users), dim3(256), lds, (hipStream_t)stream,
-                     user_list, n_users, count, cand, cap, K, n2K, nullptr,
-                     nullptr, nullptr, nullptr, 0.0f, out_score, out_item, thr, overflow, nullptr);
+  select_launch<false, false>(user_list, n_users, count, cand, cap, K, nullptr, nullptr, nullptr,
+                              nullptr, 0.0f, out_score, out_item, thr, overflow, nullptr, nullptr,
+                              0, nullptr, nullptr, nullptr, stream);
   NCF_CHECK_LAUNCH("ncf_score_select");
   return NCF_OK;
 }
@@ -1754,18 +1806,56 @@ extern "C" int ncf_score_select_rescored(const int32_t* user_list, int64_t n_use
   NCF_CHECK_ARG(n_users >= 0 && K >= 1 && cap >= K && cap <= kSelectMax,
                 "ncf_score_select_rescored: need 1 <= K <= cap <= %d", kSelectMax);
   if (n_users == 0) return NCF_OK;
-  int n2K = 1;
-  while (n2K < K) n2K <<= 1;
-  const size_t lds = sizeof(unsigned long long) * (size_t)n2K + sizeof(uint32_t) * (size_t)cap;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)k_select<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((sizeof(unsigned long long) + sizeof(uint32_t)) * kSelectMax));
-    attr = true;
-  }
-  hipLaunchKernelGGL(k_select<true>, dim3((unsigned)n_users), dim3(256), lds, (hipStream_t)stream,
-                     user_list, n_users, count, cand, cap, K, n2K, queries, items,
-                     item_bias, item_norm_max, c, out_score, out_item, thr, overflow, thr_check);
+  select_launch<true, false>(user_list, n_users, count, cand, cap, K, queries, items, item_bias,
+                             item_norm_max, c, out_score, out_item, thr, overflow, thr_check,
+                             nullptr, 0, nullptr, nullptr, nullptr, stream);
   NCF_CHECK_LAUNCH("ncf_score_select_rescored");
+  return NCF_OK;
+}
+
+// The two selects leaving out the items each user has seen (k_select<.., true>): user_ids as
+// the queries were built from (indexed like them), the users' lists as a CSR over the whole user
+// table, item_ids the index's position -> global id map (NULL: the positions are the ids).
+extern "C" int ncf_score_select_excl(const int32_t* user_list, int64_t n_users,
+                                     const uint32_t* count, const ncf_score_cand* cand,
+                                     int64_t cap, int K, float* out_score, int64_t* out_item,
+                                     float* thr, uint32_t* overflow, const float* thr_check,
+                                     const int64_t* user_ids, int64_t num_users,
+                                     const int64_t* seen_offsets, const int32_t* seen_items,
+                                     const int64_t* item_ids, void* stream) {
+  NCF_CHECK_ARG(n_users >= 0 && K >= 1 && cap >= K && cap <= kSelectMax,
+                "ncf_score_select_excl: need 1 <= K <= cap <= %d", kSelectMax);
+  NCF_CHECK_ARG(user_ids && seen_offsets && num_users >= 0,
+                "ncf_score_select_excl: user_ids and seen_offsets must be non-null");
+  if (n_users == 0) return NCF_OK;
+  select_launch<false, true>(user_list, n_users, count, cand, cap, K, nullptr, nullptr, nullptr,
+                             nullptr, 0.0f, out_score, out_item, thr, overflow, thr_check,
+                             user_ids, num_users, seen_offsets, seen_items, item_ids, stream);
+  NCF_CHECK_LAUNCH("ncf_score_select_excl");
+  return NCF_OK;
+}
+
+extern "C" int ncf_score_select_rescored_excl(const int32_t* user_list, int64_t n_users,
+                                              const uint32_t* count, const ncf_score_cand* cand,
+                                              int64_t cap, int K, const float* queries,
+                                              const float* items, const float* item_bias,
+                                              int64_t dim, const uint32_t* item_norm_max, float c,
+                                              float* out_score, int64_t* out_item, float* thr,
+                                              uint32_t* overflow, const float* thr_check,
+                                              const int64_t* user_ids, int64_t num_users,
+                                              const int64_t* seen_offsets,
+                                              const int32_t* seen_items, const int64_t* item_ids,
+                                              void* stream) {
+  NCF_CHECK_ARG(dim == 64 && queries && items && item_bias && item_norm_max,
+                "ncf_score_select_rescored_excl: dim must be 64, rows non-null");
+  NCF_CHECK_ARG(n_users >= 0 && K >= 1 && cap >= K && cap <= kSelectMax,
+                "ncf_score_select_rescored_excl: need 1 <= K <= cap <= %d", kSelectMax);
+  NCF_CHECK_ARG(user_ids && seen_offsets && num_users >= 0,
+                "ncf_score_select_rescored_excl: user_ids and seen_offsets must be non-null");
+  if (n_users == 0) return NCF_OK;
+  select_launch<true, true>(user_list, n_users, count, cand, cap, K, queries, items, item_bias,
+                            item_norm_max, c, out_score, out_item, thr, overflow, thr_check,
+                            user_ids, num_users, seen_offsets, seen_items, item_ids, stream);
+  NCF_CHECK_LAUNCH("ncf_score_select_rescored_excl");
   return NCF_OK;
 }

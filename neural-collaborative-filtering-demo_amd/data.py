@@ -163,6 +163,12 @@ class DeviceNegativeSampler:
                 chunk = torch.cat([chunk, chunk[:batch_size - chunk.numel()]])
             yield self.batch(chunk, (seed * 1_000_003 + b) & (2 ** 63 - 1))
 
+    def seen(self):
+        """Every user's positives as the ``SeenItems`` that ``score_topk(exclude=...)`` takes:
+        the sampler's own history tensors, shared, not copied."""
+        from .scoring import SeenItems
+        return SeenItems._shared(self.hist_offsets, self.hist_items, self.num_products)
+
     def check(self):
         """Raise if any batch so far held an out-of-range id (one host sync)."""
         if int(self._err.item()):

@@ -8,6 +8,10 @@ loop over users) in one HIP launch (``ncf_group_metrics``), AUC as the Mann-Whit
 (``ncf_auc_count``; sklearn's roc_auc_score with ties counted one half) over the negatives sorted
 on the device.  Same argument checks and errors.  Tie order inside a group: prediction desc,
 column asc (torch.topk / torch.sort leave it unspecified).  GPU only (no CPU fallback).
+
+``full_ranking_metrics`` is the leave-one-out protocol over the whole catalogue instead of over
+sampled negatives: the held-out item's place among all the items the user has not seen
+(``scoring.score_topk(exclude=...)``).
 """
 import warnings
 from typing import Dict, List, Optional
@@ -79,3 +83,28 @@ def calculate_metrics(predictions: torch.Tensor, targets: torch.Tensor,
     if h[base + 3] > 0:
         out["neg_accuracy"] = h[base + 4] / h[base + 3]
     return out
+
+
+def full_ranking_metrics(model, users: torch.Tensor, heldout_items: torch.Tensor, k: int,
+                         exclude=None, index=None) -> Dict[str, float]:
+    """Leave-one-out ``hr@k`` / ``ndcg@k`` / ``mrr@k`` of one held-out item per user, ranked
+    against the whole catalogue without the user's training history (``exclude``: a
+    ``scoring.SeenItems``; it must not hold the held-out items themselves).  A held-out item
+    outside the user's top k counts 0 in all three."""
+    from .scoring import score_topk
+    users = users.reshape(-1)
+    held = heldout_items.reshape(-1)
+    if users.numel() != held.numel():
+        raise ValueError("one held-out item per user")
+    if exclude is not None and bool(exclude.contains(users, held).any()):
+        raise ValueError("full_ranking_metrics: a held-out item is in its user's history")
+    _, items = score_topk(model, users, k, index, exclude=exclude)
+    hit = items == held.to(items.device, torch.int64).unsqueeze(1)     # [n, k], one hit at most
+    found = hit.any(1)
+    place = hit.to(torch.int64).argmax(1).to(torch.float64)            # 0-based, where found
+    n = max(1, users.numel())
+    hr = found.to(torch.float64).sum() / n
+    ndcg = torch.where(found, 1.0 / torch.log2(place + 2.0), torch.zeros_like(place)).sum() / n
+    mrr = torch.where(found, 1.0 / (place + 1.0), torch.zeros_like(place)).sum() / n
+    hr, ndcg, mrr = torch.stack([hr, ndcg, mrr]).tolist()
+    return {f"hr@{k}": hr, f"ndcg@{k}": ndcg, f"mrr@{k}": mrr}

@@ -18,7 +18,13 @@ rank scores all queried users against its own item shard, the per-shard top-K li
 all-gathered (RCCL) and merged per user by ``ncf_score_merge``.  ``forward_simple(hour=None)`` semantics only (the
 hour variant draws a fresh random projection on every call, architecture.py:437-442, so it has no
 reusable item side).  GPU only; no CPU fallback.
+
+``exclude=SeenItems(...)`` ranks the items a user has not seen yet instead: the select drops the
+candidates in the user's list (a CSR keyed by user id) and verifies the rest against the collect
+threshold; a user whose seen items reach into the top k is re-run from a threshold that leaves
+k unseen items at or above it (``_TopKRun.redo_excluded``).
 """
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import torch
@@ -106,6 +112,113 @@ def _param_version(model):
     return (model._engine.updates,) + tuple(p._version for p in model.parameters())
 
 
+class SeenItems:
+    """Every user's already-seen items, as a CSR over the whole user table: ``offsets`` int64
+    ``[num_users + 1]``, ``items`` int32 global item ids, sorted ascending and unique within a
+    user.  Passed as ``exclude=`` to ``score_topk`` / ``GraphedScorer`` / ``sharded_score_topk``,
+    which then rank the other items only.  Keyed by user id, not by position in a call."""
+
+    def __init__(self, users, products, num_users: int, num_products: int):
+        """From an interactions table (one ``(user, product)`` pair per row; duplicates and users
+        without a row are fine): the ``unique(u * I + p)`` construction of
+        ``DeviceNegativeSampler``.  Runs on the tensors' device (CPU tensors: no GPU needed)."""
+        users = torch.as_tensor(users).to(torch.int64).reshape(-1)
+        products = torch.as_tensor(products).to(torch.int64).reshape(-1)
+        if users.numel() != products.numel():
+            raise ValueError("users and products must have the same length")
+        if users.numel() and (int(users.min()) < 0 or int(users.max()) >= num_users or
+                              int(products.min()) < 0 or int(products.max()) >= num_products):
+            raise IndexError("interaction ids out of range")
+        key = torch.unique(users * num_products + products.to(users.device))
+        hu, hi = key // num_products, key % num_products
+        offsets = torch.zeros(num_users + 1, dtype=torch.int64, device=key.device)
+        offsets[1:] = torch.cumsum(torch.bincount(hu, minlength=num_users), 0)
+        self._set(offsets, hi.to(torch.int32), num_products)
+
+    def _set(self, offsets, items, num_products):
+        if not 0 < num_products < 2 ** 31:
+            raise ValueError("num_products must be in [1, 2^31)")
+        self.offsets, self.items, self.num_products = offsets, items, int(num_products)
+        self._lengths = None
+
+    @classmethod
+    def from_csr(cls, offsets, items, num_products: int) -> "SeenItems":
+        """From a ready CSR (validated: monotone offsets from 0 to ``len(items)``, item ids in
+        range, every user's slice sorted ascending without repeats)."""
+        offsets = torch.as_tensor(offsets).to(torch.int64).reshape(-1).contiguous()
+        items = torch.as_tensor(items).reshape(-1)
+        if offsets.numel() < 1 or int(offsets[0]) != 0 or int(offsets[-1]) != items.numel() or \
+                bool((offsets[1:] < offsets[:-1]).any()):
+            raise ValueError("SeenItems: offsets must rise from 0 to len(items)")
+        if items.numel():
+            if items.is_floating_point() or int(items.min()) < 0 or \
+                    int(items.max()) >= num_products:
+                raise ValueError("SeenItems: item id out of range")
+            # within a user (no offset between two neighbours) the ids strictly increase
+            start = torch.zeros(items.numel() + 1, dtype=torch.bool, device=offsets.device)
+            start[offsets] = True
+            if bool(((items[1:] <= items[:-1]).to(offsets.device) & ~start[1:-1]).any()):
+                raise ValueError("SeenItems: every user's items must be sorted and unique")
+        self = cls.__new__(cls)
+        self._set(offsets, items.to(device=offsets.device, dtype=torch.int32).contiguous(),
+                  num_products)
+        return self
+
+    @classmethod
+    def _shared(cls, offsets, items, num_products):
+        """Around tensors that already hold a valid CSR, without a copy."""
+        self = cls.__new__(cls)
+        self._set(offsets, items, num_products)
+        return self
+
+    @property
+    def num_users(self) -> int:
+        return self.offsets.numel() - 1
+
+    @property
+    def device(self):
+        return self.offsets.device
+
+    @property
+    def lengths(self) -> torch.Tensor:
+        """Seen items per user, int64 ``[num_users]``."""
+        if self._lengths is None:
+            self._lengths = self.offsets[1:] - self.offsets[:-1]
+        return self._lengths
+
+    def to(self, device) -> "SeenItems":
+        return SeenItems._shared(self.offsets.to(device), self.items.to(device), self.num_products)
+
+    def contains(self, users: torch.Tensor, items: torch.Tensor) -> torch.Tensor:
+        """Per pair, whether ``items[j]`` is in ``users[j]``'s list (torch ops on ``device``)."""
+        u = users.to(device=self.device, dtype=torch.int64).reshape(-1)
+        it = items.to(device=self.device, dtype=torch.int64).reshape(-1)
+        if self.items.numel() == 0:
+            return torch.zeros_like(u, dtype=torch.bool)
+        owner = torch.repeat_interleave(torch.arange(self.num_users, device=self.device),
+                                        self.lengths)
+        keys = owner * self.num_products + self.items.to(torch.int64)   # sorted ascending
+        want = u * self.num_products + it
+        pos = torch.searchsorted(keys, want).clamp_max(keys.numel() - 1)
+        return keys[pos] == want
+
+
+def _check_exclude(exclude, num_users: int, num_products: int, device=None):
+    """The ``exclude=`` argument against the model it is used with (before any launch)."""
+    if exclude is None:
+        return
+    if not isinstance(exclude, SeenItems):
+        raise TypeError("exclude must be a SeenItems")
+    if exclude.num_users != num_users:
+        raise ValueError(f"exclude covers {exclude.num_users} users, the model has {num_users}")
+    if exclude.num_products != num_products:
+        raise ValueError(f"exclude is over {exclude.num_products} items, the model has "
+                         f"{num_products}")
+    if device is not None and exclude.device != device:
+        raise ValueError(f"exclude is on {exclude.device}, the index on {device}: "
+                         "move it with exclude.to(device)")
+
+
 # the candidate scan on bf16 matrix cores with split operands (fp32 accuracy, same candidate
 # sets; an index without the planes, p3 = None, takes the fp32 MFMA scan)
 SPLIT_SCAN = True
@@ -160,6 +273,7 @@ SORT_USERS = False
 # expected_per_user: fewer per-wave LDS slice overflows; tested invisible in the results)
 SIZED_SPLIT = True
 KTH_LDS_MAX = 38912   # = score.hip kKthLdsMax
+SELECT_MAX = 8192     # = score.hip kSelectMax: the longest candidate list the select takes
 # the threshold sample on bf16 matrix cores, fp16 logits rounded down (ncf_score_sample_split16 +
 # ncf_score_kth16, its k-th lowered by the two-term bound) instead of the fp32 sample GEMM +
 # fp32 k-th (measured, 10K x 1M eager: top-100 4.25 -> 3.73 ms, top-10 2.78 -> 2.70); needs the
@@ -171,11 +285,24 @@ SAMPLE16 = True
 SAMPLE_GROUP = 8
 
 
-def _select(idx, rows, n, run, k, out_s, out_i, overflow, st, terms=None, check=None):
+def _select(idx, rows, n, run, k, out_s, out_i, overflow, st, terms=None, check=None,
+            exclude=None):
     """ncf_score_select(_rescored) of n users' candidate lists (fp32 re-scoring after a one- or
     two-term scan; ``terms`` as the scan's; ``check``: the rank-j thresholds to verify the
-    selection against, flag 2 where it is not provably the top k)."""
-    if idx.pmax is not None:
+    selection against, flag 2 where it is not provably the top k; ``exclude``: the users' seen
+    items, looked up by ``run.uid`` and dropped from the lists first, ncf_score_select*_excl)."""
+    if exclude is not None:
+        seen = (ptr(run.uid), exclude.num_users, ptr(exclude.offsets), ptr(exclude.items),
+                ptr(idx.ids))
+        if idx.pmax is not None:
+            _lib.call("ncf_score_select_rescored_excl", rows, n, ptr(run.count), ptr(run.cand),
+                      run.cap, k, ptr(run.q), ptr(idx.p), ptr(idx.bias), idx.p.shape[1],
+                      ptr(idx.pmax), MARGIN_C[terms or _terms(idx)], out_s, out_i, ptr(run.thr),
+                      overflow, check, *seen, st)
+        else:
+            _lib.call("ncf_score_select_excl", rows, n, ptr(run.count), ptr(run.cand), run.cap, k,
+                      out_s, out_i, ptr(run.thr), overflow, check, *seen, st)
+    elif idx.pmax is not None:
         _lib.call("ncf_score_select_rescored", rows, n, ptr(run.count), ptr(run.cand), run.cap, k, ptr(run.q), ptr(idx.p), ptr(idx.bias),
                   idx.p.shape[1], ptr(idx.pmax), MARGIN_C[terms or _terms(idx)], out_s, out_i,
                   ptr(run.thr), overflow, check, st)
@@ -224,13 +351,15 @@ class _TopKRun:
     """Buffers and launch sequence of one top-k pipeline for ``n`` users (shared by the eager
     ``score_topk`` and the captured ``GraphedScorer``)."""
 
-    def __init__(self, index: "ItemIndex", n: int, k: int, cap: int):
+    def __init__(self, index: "ItemIndex", n: int, k: int, cap: int,
+                 exclude: Optional[SeenItems] = None):
         p = index.p
         dev = p.device
         I, D = p.shape
         if not 1 <= k <= min(I, cap):
             raise ValueError(f"k must be in [1, {min(I, cap)}]")
         self.index, self.n, self.k, self.cap = index, n, k, cap
+        self.exclude = exclude
         s16 = SAMPLE16 and index.p3 is not None and index.pmax is not None
         self.j = _threshold_rank(k, cap, s16)
         self.S = _sample_size(I, k, cap, self.j)
@@ -252,8 +381,10 @@ class _TopKRun:
             self.S // SAMPLE_GROUP >= 8 * self.j else 1
         self.Sg = -(-self.S // self.G)
         self.q, self.thr = e(max(n, 1), D), e(max(n, 1))
-        # the rank-j thresholds before the margins (the select's check)
-        self.thr_chk = e(max(n, 1)) if self.j < k else None
+        # the rank-j thresholds before the margins (the select's check).  With exclusion every
+        # threshold is checked: it bounds the k-th logit of the catalogue, not of the unseen
+        # items (there: the guaranteed thresholds, after the sample's own margin)
+        self.thr_chk = e(max(n, 1)) if self.j < k or exclude is not None else None
         self.sample = (torch.empty(max(n, 1), self.Sg, dtype=torch.int16, device=dev) if self.s16
                        else e(max(n, 1), self.S))
         self.count = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
@@ -279,16 +410,20 @@ class _TopKRun:
             _lib.call("ncf_score_sample_split16", ptr(self.q), n, ptr(idx.p3), I, D, self.stride,
                       ptr(self.sbias), self.S, self.G, ptr(self.sample), st)
             _lib.call("ncf_score_kth16", ptr(self.sample), n, self.Sg, self.j, ptr(self.thr), st)
-            if self.thr_chk is not None:
+            if self.thr_chk is not None and self.exclude is None:
                 self.thr_chk.copy_(self.thr)
             # (the k-th of the fp16 sample is a bound after the two-term error is taken off)
             _lib.call("ncf_score_margin", ptr(self.q), None, n, D, ptr(idx.pmax), MARGIN_C[2],
                       ptr(self.thr), st)
+            if self.exclude is not None:
+                self.thr_chk.copy_(self.thr)
         else:
             _lib.call("ncf_gemm_f32", n, self.S, D, ptr(self.q), D, 0, ptr(p), D * self.stride, 1,
                       ptr(self.sample), self.S, ptr(self.sbias), 0, st)
             _lib.call("ncf_score_kth", ptr(self.sample), n, self.S, k, None, self.stride,
                       ptr(self.thr), st)
+            if self.thr_chk is not None:   # (exclusion only: this plan's rank is k)
+                self.thr_chk.copy_(self.thr)
         self.count.zero_()
         # the scan's users in threshold order (SORT_USERS): its 32-user blocks then hold users of
         # near-equal thresholds, so its first reject (a lane's best logit against the smallest
@@ -301,21 +436,28 @@ class _TopKRun:
         _collect(idx, ptr(self.q), rows, n, ptr(self.thr), cap, ptr(self.count), ptr(self.cand),
                  st, expected=-(-self.j * I // self.S) if SIZED_SPLIT else 0)
         _select(idx, None, n, self, k, ptr(self.scores), ptr(self.items), ptr(self.overflow), st,
-                check=None if self.thr_chk is None else ptr(self.thr_chk))
+                check=None if self.thr_chk is None else ptr(self.thr_chk), exclude=self.exclude)
 
-    def safe_thresholds(self, redo, st):
+    def safe_thresholds(self, redo, st, rank=None, cap=None):
         """Users flagged by the rank-j check: their threshold from the sample's k-th instead (the
         fp32 sample GEMM over the same strided items, its k-th: k sample items at or above it, a
-        guaranteed bound; the re-run's collect lowers it by the scan's margin)."""
-        idx, k = self.index, self.k
+        guaranteed bound; the re-run's collect lowers it by the scan's margin).  ``rank``: the
+        sample rank to take instead of k (exclusion: k + the longest list of these users, so k
+        unseen items are at or above it; -inf where the sample is smaller than that), for
+        candidate lists of ``cap``."""
+        idx, k = self.index, rank or self.k
+        cap = cap or self.cap
         p = idx.p
         I, D = p.shape
+        if k > _sample_size(I, k, cap):
+            self.thr[redo] = float("-inf")
+            return
         q = self.q[redo].contiguous()
         nr = q.shape[0]
         # (a sample sized for the k-th itself, ~k I / S candidates within cap: the rank-j
         # sample's S ~ I / k would expect ~k^2 of them, over the cap at k = 100, and cost every
         # flagged user a further overflow round; ADVICE r4)
-        S = _sample_size(I, k, self.cap)
+        S = _sample_size(I, k, cap)
         stride = I // S
         sbias = idx.bias[::stride][:S].contiguous()
         sample = torch.empty(nr, S, device=p.device)
@@ -329,6 +471,8 @@ class _TopKRun:
         """Re-run the users whose candidate list overflowed (flag 1) or whose rank-j result was
         not provably exact (flag 2) (eager; rare: the threshold sample targets cap / 2
         candidates at most, and a rank-j shortfall has probability ~1e-14 per user)."""
+        if self.exclude is not None:
+            return self.redo_excluded(st)
         idx, k, cap = self.index, self.k, self.cap
         p, bias = idx.p, idx.bias
         I, D = p.shape
@@ -360,26 +504,83 @@ class _TopKRun:
             overflow[redo] = sub_o
         raise RuntimeError("score_topk: candidate lists kept overflowing (degenerate scores?)")
 
+    def redo_excluded(self, st):
+        """redo_overflow with exclusion: the flagged users (1: the list overflowed; 2: fewer than
+        k unseen candidates at or above the checked threshold) re-run in buffers of their own.
+        Flag 2 takes the fp32 sample's rank k + e as the threshold, e the longest list among the
+        flagged users: at least k + e items are at or above it and at most e of them are seen.
+        The lists hold cap_r >= k + e candidates, so an overflowing list always shows the select k
+        unseen ones and the threshold it returns (their k-th) rises every round."""
+        idx, k, ex = self.index, self.k, self.exclude
+        dev = idx.p.device
+        overflow = self.overflow[:self.n]
+        redo = torch.nonzero(overflow).flatten()
+        if redo.numel() == 0:
+            return
+        uid = self.uid[redo]
+        ok = (uid >= 0) & (uid < ex.num_users)   # (an id out of range raises after this)
+        e = int((ex.lengths[uid.clamp(0, ex.num_users - 1)] * ok).max())
+        if k + e > SELECT_MAX:
+            raise ValueError(f"score_topk: k + the longest seen list ({k} + {e}) exceeds the "
+                             f"select's {SELECT_MAX} candidates")
+        cap_r = max(self.cap, min(SELECT_MAX, 2 * (k + e)))
+        short = redo[overflow[redo] == 2]
+        if short.numel():
+            self.safe_thresholds(short, st, rank=k + e, cap=cap_r)
+        nr = redo.numel()
+        sub = SimpleNamespace(
+            q=self.q[redo].contiguous(), uid=uid.contiguous(), thr=self.thr[redo].contiguous(),
+            count=torch.zeros(nr, dtype=torch.int32, device=dev), cap=cap_r,
+            cand=torch.empty(nr, cap_r, 2, dtype=torch.int32, device=dev))
+        terms = max(2, _terms(idx))   # (as redo_overflow)
+        rows = torch.arange(nr, dtype=torch.int32, device=dev)
+        for _ in range(32):
+            m = rows.numel()
+            sub_s = torch.empty(m, k, device=dev)
+            sub_i = torch.empty(m, k, dtype=torch.int64, device=dev)
+            sub_o = torch.empty(m, dtype=torch.int32, device=dev)
+            sub.count.zero_()
+            _collect(idx, ptr(sub.q), ptr(rows), m, ptr(sub.thr), cap_r, ptr(sub.count),
+                     ptr(sub.cand), st, terms=terms)
+            _select(idx, ptr(rows), m, sub, k, ptr(sub_s), ptr(sub_i), ptr(sub_o), st,
+                    terms=terms, exclude=ex)
+            dst = redo[rows.long()]
+            self.scores[dst] = sub_s
+            self.items[dst] = sub_i
+            rows = rows[sub_o != 0]
+            if rows.numel() == 0:
+                overflow.zero_()
+                return
+        raise RuntimeError("score_topk: candidate lists kept overflowing (degenerate scores?)")
+
     def result(self):
         items = self.items
         if self.index.ids is not None:   # shard-local positions -> global item ids
-            items = self.index.ids[items.clamp_min(0)]
+            if self.exclude is None:
+                items = self.index.ids[items.clamp_min(0)]
+            else:   # (a shard may run out of unseen items: its empty slots stay -1)
+                items = torch.where(items < 0, items, self.index.ids[items.clamp_min(0)])
         return self.scores, items
 
 
 def score_topk(model, user_ids: torch.Tensor, k: int = 10, index: Optional[ItemIndex] = None,
-               cap: int = 8192) -> Tuple[torch.Tensor, torch.Tensor]:
+               cap: int = 8192, *,
+               exclude: Optional[SeenItems] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k (probability, item id) per user over all items, as
     ``forward_simple(user, all_items)`` + ``nlargest(k)`` would rank them.  Returns
-    ``(scores [n, k] fp32, items [n, k] int64)``."""
+    ``(scores [n, k] fp32, items [n, k] int64)``.  ``exclude``: every user's seen items
+    (``SeenItems``, on the index's device): the top k of the others instead, exact by the same
+    order; a user with fewer than k unseen items gets trailing ``(0.0, -1)`` slots."""
+    _check_exclude(exclude, model.num_users, model.num_products)
     if index is None:
         index = ItemIndex(model)
     elif not index.valid_for(model):   # parameters changed since the index was built
         index = ItemIndex(model, items=index.ids)
     dev = index.p.device
+    _check_exclude(exclude, model.num_users, model.num_products, dev)
     uid = user_ids.to(device=dev, dtype=torch.int64).contiguous()
     n = uid.numel()
-    run = _TopKRun(index, n, k, cap)
+    run = _TopKRun(index, n, k, cap, exclude=exclude)
     if n == 0:
         return run.result()
     st = _lib.stream_ptr(dev)
@@ -405,13 +606,19 @@ class GraphedScorer:
     The graph writes into static output tensors.  By default a call returns fresh copies of
     them (like ``score_topk``); ``scorer(user_ids, copy=False)`` returns the static tensors
     themselves, which the NEXT call overwrites in place.
+
+    ``exclude`` (``SeenItems``) as in ``score_topk``.  The lists are looked up by user id inside
+    the graph, so it holds the CSR's two pointers only and any users can be replayed; users whose
+    seen items reach into their top k take the eager re-run after the replay.
     """
 
     def __init__(self, model, n_users: int, k: int = 10, index: Optional[ItemIndex] = None,
-                 cap: int = 8192):
+                 cap: int = 8192, *, exclude: Optional[SeenItems] = None):
         self.model, self.n, self.k, self.cap = model, int(n_users), int(k), cap
         if self.n < 1:
             raise ValueError("GraphedScorer needs n_users >= 1")
+        _check_exclude(exclude, model.num_users, model.num_products)
+        self.exclude = exclude
         self.index = index if index is not None and index.valid_for(model) else ItemIndex(
             model, items=None if index is None else index.ids)
         self._capture()
@@ -419,7 +626,8 @@ class GraphedScorer:
     def _capture(self):
         idx = self.index
         dev = idx.p.device
-        self.run = run = _TopKRun(idx, self.n, self.k, self.cap)
+        _check_exclude(self.exclude, self.model.num_users, self.model.num_products, dev)
+        self.run = run = _TopKRun(idx, self.n, self.k, self.cap, exclude=self.exclude)
         run.uid.zero_()
         st = _lib.stream_ptr(dev)
         run.launch(self.model, st)           # warm-up: kernel attributes, lazy module loads
@@ -480,12 +688,15 @@ def merge_topk(cand_scores: torch.Tensor, cand_items: torch.Tensor, k: int):
 
 def sharded_score_topk(model, user_ids: torch.Tensor, k: int = 10,
                        index: Optional[ItemIndex] = None, group=None, cap: int = 8192,
-                       local_topk=None, merge=None, graph: bool = False):
+                       local_topk=None, merge=None, graph: bool = False, *,
+                       exclude: Optional[SeenItems] = None):
     """Item-sharded C5 scoring over ``torch.distributed``: rank r scores every
     queried user against ``shard_items(I, W, r)``, the ``[n, k]`` local lists are all-gathered
     (8 B per entry + id widening) and merged per user.  Every rank returns the global top-k.
     ``local_topk(user_ids, k) -> (scores, global ids)`` and ``merge`` default to the HIP path
-    (they are parameters so the collective layout can be exercised on CPU ranks)."""
+    (they are parameters so the collective layout can be exercised on CPU ranks).  ``exclude``
+    (``SeenItems``, global item ids, the same on every rank) as in ``score_topk``: each shard
+    leaves out the seen items it holds."""
     import torch.distributed as dist
     W = dist.get_world_size(group) if dist.is_initialized() else 1
     r = dist.get_rank(group) if dist.is_initialized() else 0
@@ -497,12 +708,15 @@ def sharded_score_topk(model, user_ids: torch.Tensor, k: int = 10,
         def local_topk(u, _k):
             if graph:   # the shard's pipeline as a captured hipGraph (cached on the index)
                 gs = index.__dict__.setdefault("_graphed", {})
-                sc = gs.get((u.numel(), kk, cap))
+                # (a scorer keeps its SeenItems alive, so the id in the key stays its own)
+                key = (u.numel(), kk, cap) + (() if exclude is None else (id(exclude),))
+                sc = gs.get(key)
                 if sc is None:
-                    sc = gs[(u.numel(), kk, cap)] = GraphedScorer(model, u.numel(), kk, index, cap)
+                    sc = gs[key] = GraphedScorer(model, u.numel(), kk, index, cap,
+                                                 exclude=exclude)
                 s, i = sc(u)
             else:
-                s, i = score_topk(model, u, kk, index, cap)
+                s, i = score_topk(model, u, kk, index, cap, exclude=exclude)
             if kk < _k:   # a shard smaller than k: pad with empty slots
                 s = torch.cat([s, s.new_zeros(s.shape[0], _k - kk)], 1)
                 i = torch.cat([i, i.new_full((i.shape[0], _k - kk), -1)], 1)
