@@ -653,6 +653,14 @@ int ncf_score_queries(const int64_t* user_ids, int64_t n, const float* mf_user, 
                       int64_t dim, const float* mf_gamma, const float* mf_beta, float eps,
                       const float* mf_out_w, const float* final_w, float* queries, int* err_flag,
                       void* stream);
+/* ncf_score_queries with forward_simple's hour: row r times scale[hours[r]] (scale fp32 [24, dim],
+ * s_h = 1 + 0.3 tp_h; one fp32 multiply per element after the plain row is formed, the pad stays
+ * zero).  An hour outside [0, 24) ORs 2 into err_flag and takes hour 0 (a bad user id: 1, row 0). */
+int ncf_score_queries_hour(const int64_t* user_ids, const int64_t* hours, int64_t n,
+                           const float* mf_user, int64_t rows, int64_t dim, const float* mf_gamma,
+                           const float* mf_beta, float eps, const float* mf_out_w,
+                           const float* final_w, const float* scale, float* queries,
+                           int* err_flag, void* stream);
 int ncf_score_item_bias(const float* mlp_item, int64_t n, const float* final_w,
                         const float* final_b, const float* mf_out_b, float* bias, void* stream);
 /* ncf_score_kth: logit(u, j) = logits[u*S + j] + item_bias[j*stride]; item_bias may be NULL

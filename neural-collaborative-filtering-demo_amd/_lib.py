@@ -185,6 +185,7 @@ SIGNATURES = {
     "ncf_adam_flat_clock": (I32, [P, P, P, P, I64, P, I32, P, F64, F64, F64, F64, P]),
     "ncf_adam_flat_clock_close": (I32, [P, P, P, P, I64, P, I32, P, F64, F64, F64, F64, U64, P]),
     "ncf_score_queries": (I32, [P, I64, P, I64, I64, P, P, F32, P, P, P, P, P]),
+    "ncf_score_queries_hour": (I32, [P, P, I64, P, I64, I64, P, P, F32, P, P, P, P, P, P]),
     "ncf_score_item_bias": (I32, [P, I64, P, P, P, P, P]),
     "ncf_score_kth": (I32, [P, I64, I64, I32, P, I64, P, P]),
     "ncf_score_sample_split16": (I32, [P, I64, P, I64, I64, I64, P, I64, I64, P, P]),

@@ -50,13 +50,18 @@ __device__ __forceinline__ float fkey_inv(uint32_t k) {
 // ---- 1. queries: q = w0 * LN(U_mf[id]) (.) w_mf; L = D/4 lanes per row.  The rows are QD =
 // max(64, D) floats wide: a D < 64 row is zero-padded (the item index pads its rows the same way,
 // so every dot product is the D-term one — the scan kernels are 64-deep; D = 128 rows are
-// scanned 128-deep by the fp32 scan, k_collect<128>)
-template <int D, int kQD = (D > 64 ? D : 64)>
+// scanned 128-deep by the fp32 scan, k_collect<128>).  HOUR (ncf_score_queries_hour): the row
+// times scale[hours[r]] (forward_simple's hour path: s_h = 1 + 0.3 tp_h, a [24, D] table), one
+// more fp32 multiply per element after the row is formed, so an all-ones table leaves the bits of
+// the plain row; an hour outside [0, 24) flags bit 2 and takes hour 0; the pad stays zero
+template <int D, bool HOUR = false, int kQD = (D > 64 ? D : 64)>
 __global__ void k_queries(const int64_t* __restrict__ ids, int64_t n, const float* __restrict__ table,
                           int64_t rows, const float* __restrict__ gamma,
                           const float* __restrict__ beta, float eps,
                           const float* __restrict__ w_mf, const float* __restrict__ final_w,
-                          float* __restrict__ q, int* __restrict__ err) {
+                          float* __restrict__ q, int* __restrict__ err,
+                          const int64_t* __restrict__ hours = nullptr,
+                          const float* __restrict__ scale = nullptr) {
   constexpr int L = D / 4;
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t r = t / L;
@@ -74,10 +79,20 @@ __global__ void k_queries(const int64_t* __restrict__ ids, int64_t n, const floa
   const float rstd = 1.0f / sqrtf(var + eps);
   const float4 g = ld4(gamma + c), b = ld4(beta + c), w = ld4(w_mf + c);
   const float w0 = final_w[0];
-  st4(q + r * kQD + c, make_float4(w0 * ((xc.x * rstd * g.x + b.x) * w.x),
-                                   w0 * ((xc.y * rstd * g.y + b.y) * w.y),
-                                   w0 * ((xc.z * rstd * g.z + b.z) * w.z),
-                                   w0 * ((xc.w * rstd * g.w + b.w) * w.w)));
+  float4 o = make_float4(w0 * ((xc.x * rstd * g.x + b.x) * w.x),
+                         w0 * ((xc.y * rstd * g.y + b.y) * w.y),
+                         w0 * ((xc.z * rstd * g.z + b.z) * w.z),
+                         w0 * ((xc.w * rstd * g.w + b.w) * w.w));
+  if constexpr (HOUR) {
+    int64_t h = hours[r];
+    if (h < 0 || h >= 24) {
+      if (err && c == 0) atomicOr(err, 2);
+      h = 0;
+    }
+    const float4 s = ld4(scale + h * D + c);
+    o = make_float4(o.x * s.x, o.y * s.y, o.z * s.z, o.w * s.w);
+  }
+  st4(q + r * kQD + c, o);
 #pragma unroll
   for (int pc = D + c; pc < kQD; pc += D) st4(q + r * kQD + pc, make_float4(0.f, 0.f, 0.f, 0.f));
 }
@@ -1481,10 +1496,32 @@ extern "C" int ncf_score_queries(const int64_t* user_ids, int64_t n, const float
   if (dim == DD)                                                                                  \
     hipLaunchKernelGGL(k_queries<DD>, dim3(ncf_cdiv(n * (DD / 4), 256)), dim3(256), 0,            \
                        (hipStream_t)stream, user_ids, n, mf_user, rows, mf_gamma, mf_beta, eps,     \
-                       mf_out_w, final_w, queries, err_flag);
+                       mf_out_w, final_w, queries, err_flag, nullptr, nullptr);
   NCF_QUERIES(16) NCF_QUERIES(32) NCF_QUERIES(64) NCF_QUERIES(128)
 #undef NCF_QUERIES
   NCF_CHECK_LAUNCH("ncf_score_queries");
+  return NCF_OK;
+}
+
+extern "C" int ncf_score_queries_hour(const int64_t* user_ids, const int64_t* hours, int64_t n,
+                                      const float* mf_user, int64_t rows, int64_t dim,
+                                      const float* mf_gamma, const float* mf_beta, float eps,
+                                      const float* mf_out_w, const float* final_w,
+                                      const float* scale, float* queries, int* err_flag,
+                                      void* stream) {
+  NCF_CHECK_ARG(n >= 0 && (dim == 16 || dim == 32 || dim == 64 || dim == 128),
+                "ncf_score_queries_hour: dim must be 16, 32, 64 or 128");
+  if (n == 0) return NCF_OK;
+  NCF_CHECK_ARG(hours != nullptr && scale != nullptr,
+                "ncf_score_queries_hour: hours and scale are required");
+#define NCF_QUERIES(DD)                                                                           \
+  if (dim == DD)                                                                                  \
+    hipLaunchKernelGGL((k_queries<DD, true>), dim3(ncf_cdiv(n * (DD / 4), 256)), dim3(256), 0,    \
+                       (hipStream_t)stream, user_ids, n, mf_user, rows, mf_gamma, mf_beta, eps,     \
+                       mf_out_w, final_w, queries, err_flag, hours, scale);
+  NCF_QUERIES(16) NCF_QUERIES(32) NCF_QUERIES(64) NCF_QUERIES(128)
+#undef NCF_QUERIES
+  NCF_CHECK_LAUNCH("ncf_score_queries_hour");
   return NCF_OK;
 }
 

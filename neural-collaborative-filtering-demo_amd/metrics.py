@@ -86,11 +86,12 @@ def calculate_metrics(predictions: torch.Tensor, targets: torch.Tensor,
 
 
 def full_ranking_metrics(model, users: torch.Tensor, heldout_items: torch.Tensor, k: int,
-                         exclude=None, index=None) -> Dict[str, float]:
+                         exclude=None, index=None, hour=None) -> Dict[str, float]:
     """Leave-one-out ``hr@k`` / ``ndcg@k`` / ``mrr@k`` of one held-out item per user, ranked
     against the whole catalogue without the user's training history (``exclude``: a
     ``scoring.SeenItems``; it must not hold the held-out items themselves).  A held-out item
-    outside the user's top k counts 0 in all three."""
+    outside the user's top k counts 0 in all three.  ``hour``: the hour of day every held-out
+    interaction carries (an int, or one per user), ranked as ``score_topk(hour=)`` does."""
     from .scoring import score_topk
     users = users.reshape(-1)
     held = heldout_items.reshape(-1)
@@ -98,7 +99,7 @@ def full_ranking_metrics(model, users: torch.Tensor, heldout_items: torch.Tensor
         raise ValueError("one held-out item per user")
     if exclude is not None and bool(exclude.contains(users, held).any()):
         raise ValueError("full_ranking_metrics: a held-out item is in its user's history")
-    _, items = score_topk(model, users, k, index, exclude=exclude)
+    _, items = score_topk(model, users, k, index, exclude=exclude, hour=hour)
     hit = items == held.to(items.device, torch.int64).unsqueeze(1)     # [n, k], one hit at most
     found = hit.any(1)
     place = hit.to(torch.int64).argmax(1).to(torch.float64)            # 0-based, where found

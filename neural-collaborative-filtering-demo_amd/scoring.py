@@ -15,9 +15,20 @@ of the catalogue: one rank's item shard); ``score_topk`` runs the threshold / MF
 select pipeline (``GraphedScorer``: the same pipeline captured once as a hipGraph and replayed);
 ``sharded_score_topk`` is the item-sharded multi-GPU form: every
 rank scores all queried users against its own item shard, the per-shard top-K lists are
-all-gathered (RCCL) and merged per user by ``ncf_score_merge``.  ``forward_simple(hour=None)`` semantics only (the
-hour variant draws a fresh random projection on every call, architecture.py:437-442, so it has no
-reusable item side).  GPU only; no CPU fallback.
+all-gathered (RCCL) and merged per user by ``ncf_score_merge``.  GPU only; no CPU fallback.
+
+``hour=`` ranks as ``forward_simple(user, all_items, hour)`` does (the reference's serving
+default, app.py:43-77).  The hour path factorises the same way:
+
+    logit(u, i, h) = (q_u * s_h) . p_i + bias_{h,i}
+    s_h        = 1 + 0.3 * tp_h,  tp_h = hour_E[h], or proj(hour_E[h]) when T != D
+    bias_{h,i} = w1 * mlp_item(i, h) + w0 * b_mf + b_final
+
+so the item rows stay as they are, the hour scales the query (ncf_score_queries_hour, a 24-row
+table built once per index) and picks the item bias (one vector per hour, built on first use
+and cached on the index); everything after the queries runs unchanged on ``ItemIndex.at_hour``.
+Where ``temporal_dim != mf_embedding_dim`` the reference draws a fresh random projection on
+every call (architecture.py:437-442); a ranking needs one fixed projection, given to the index.
 
 ``exclude=SeenItems(...)`` ranks the items a user has not seen yet instead: the select drops the
 candidates in the user's list (a CSR keyed by user id) and verifies the rest against the collect
@@ -41,11 +52,19 @@ QD = 64   # the scan's row width (ncf_score_queries pads narrower rows to it)
 class ItemIndex:
     """Item-side factors of the factorised scorer for one model state."""
 
-    def __init__(self, model, chunk: int = 65536, items: Optional[torch.Tensor] = None):
-        """``items``: the global item ids this index covers (default: the whole catalogue)."""
+    def __init__(self, model, chunk: int = 65536, items: Optional[torch.Tensor] = None, *,
+                 projection=None):
+        """``items``: the global item ids this index covers (default: the whole catalogue).
+        ``projection``: the ``nn.Linear(T, D)`` (or ``(weight, bias)``) of the hour path, as
+        ``ops.forward_simple_hour`` takes it; needed to score at an hour when ``temporal_dim !=
+        mf_embedding_dim``, unused otherwise."""
         eng = model._engine
         eng.sync_tables()
         self.model = model
+        self.projection = projection
+        self.chunk = chunk
+        self.scale = None        # [24, D] s_h = 1 + 0.3 tp_h (hour_table)
+        self._hour_bias = {}     # hour -> bias_{h, .} over this index's items
         dev = model.mf_norm.weight.device
         if dev.type != "cuda":
             raise RuntimeError("ncf_amd scoring runs on the MI355X only (no CPU fallback)")
@@ -69,6 +88,7 @@ class ItemIndex:
             I = ids.numel()
         table = model.mf_embedding_collection.embedding_bags["product_id"].weight
         self.dim = D
+        self._item_ids = ids
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         pD = torch.empty(I, D, device=dev)
         _lib.call("ncf_gather_rows", ptr(ids), I, ptr(table), model.num_products, D,
@@ -101,10 +121,118 @@ class ItemIndex:
             if SPLIT_TERMS < 3:
                 self.pmax = torch.empty(1, dtype=torch.int32, device=dev)
                 _lib.call("ncf_score_item_norm_max", ptr(self.p), I, QD, ptr(self.pmax), st)
-        self.version = _param_version(model)
+        self.version = _param_version(model) + self._projection_version()
 
     def valid_for(self, model) -> bool:
-        return model is self.model and self.version == _param_version(model)
+        return model is self.model and \
+            self.version == _param_version(model) + self._projection_version()
+
+    def _projection_tensors(self):
+        pr = self.projection
+        if pr is None:
+            return ()
+        return tuple(pr) if isinstance(pr, (tuple, list)) else (pr.weight, pr.bias)
+
+    def _projection_version(self):
+        # (in-place changes of the projection's tensors make the hour biases stale as well)
+        return tuple(t._version for t in self._projection_tensors())
+
+    def owns_projection(self, projection) -> bool:
+        """Whether ``projection`` is this index's own (the same module, or the same tensors)."""
+        if projection is self.projection:
+            return True
+        if projection is None or self.projection is None:
+            return False
+        mine = self._projection_tensors()
+        theirs = tuple(projection) if isinstance(projection, (tuple, list)) else \
+            (projection.weight, projection.bias)
+        return len(mine) == len(theirs) and all(a is b for a, b in zip(mine, theirs))
+
+    def hour_table(self) -> torch.Tensor:
+        """The 24 query scales s_h = 1 + 0.3 tp_h, fp32 ``[24, D]`` (built once): tp_h is
+        ``hour_E[h]``, projected to D columns when ``temporal_dim != mf_embedding_dim``
+        (architecture.py:434-444), by the kernels ``forward_simple_hour`` uses."""
+        if self.scale is not None:
+            return self.scale
+        from .sparse import gather_rows
+        m = self.model
+        D, T = m.mf_embedding_dim, m.temporal_dim
+        if D != m.mlp_embedding_dim:
+            # (as forward_simple(hour): the reference scales the MLP item rows by a vector of
+            # the MF width, architecture.py:436-456, a broadcast error unless the widths agree)
+            raise RuntimeError(f"forward_simple(hour): the temporal scale has {D} columns, the "
+                               f"MLP item rows {m.mlp_embedding_dim}")
+        dev = self.p.device
+        if T != D and self.projection is None:
+            raise ValueError(
+                f"scoring at an hour with temporal_dim {T} != mf_embedding_dim {D} needs "
+                "ItemIndex(..., projection=nn.Linear(T, D)): the reference draws a fresh random "
+                "projection on every call (architecture.py:437-442), and a ranking needs one "
+                "fixed projection")
+        te = gather_rows(m.temporal_encoding.hour_embed.weight,
+                         torch.arange(24, dtype=torch.int64, device=dev))
+        if T != D:
+            w_p, b_p = self._projection_tensors()
+            w_p = w_p.detach().to(device=dev, dtype=torch.float32).contiguous()
+            b_p = b_p.detach().to(device=dev, dtype=torch.float32).contiguous()
+            tp = torch.empty(24, D, device=dev)
+            _lib.call("ncf_gemm_f32", 24, D, T, ptr(te), T, 0, ptr(w_p), T, 1, ptr(tp), D,
+                      ptr(b_p), 0, _lib.stream_ptr(dev))
+        else:
+            tp = te
+        self._te, self._tp = te, tp
+        self.scale = (1.0 + 0.3 * tp).contiguous()
+        return self.scale
+
+    def hour_bias(self, hour: int) -> torch.Tensor:
+        """bias_{h, i} = w1 * mlp_item(i, h) + w0 * b_mf + b_final over this index's items, built
+        on first use (the chunked eval forward of ``__init__`` with the hour's ``temporal=``) and
+        kept while the index is valid."""
+        hour = int(hour)
+        if not 0 <= hour < 24:
+            raise IndexError(f"hour {hour} is outside [0, 24)")
+        b = self._hour_bias.get(hour)
+        if b is not None:
+            return b
+        self.hour_table()
+        model, ids = self.model, self._item_ids
+        eng = model._engine
+        dev = self.p.device
+        I = ids.numel()
+        cn = max(1, min(I, self.chunk))
+        tp_rows = self._tp[hour].expand(cn, -1).contiguous()
+        te_rows = self._te[hour].expand(cn, -1).contiguous()
+        zeros = torch.zeros(cn, dtype=torch.int64, device=dev)
+        mlp_item = torch.empty(I, device=dev)
+        with torch.no_grad():
+            for c0 in range(0, I, cn):
+                c1 = min(I, c0 + cn)
+                w = eng.forward(zeros[:c1 - c0], ids[c0:c1], 1, False, 0.0, 0,
+                                temporal=(tp_rows[:c1 - c0], 0.3, te_rows[:c1 - c0]))
+                mlp_item[c0:c1].copy_(w.mlp_pred)
+        b = torch.empty(I, device=dev)
+        _lib.call("ncf_score_item_bias", ptr(mlp_item), I, ptr(model.final[0].weight),
+                  ptr(model.final[0].bias), ptr(model.mf_output.bias), ptr(b),
+                  _lib.stream_ptr(dev))
+        self._hour_bias[hour] = b
+        return b
+
+    def at_hour(self, hour: int, bias: Optional[torch.Tensor] = None) -> "HourView":
+        """This index as the pipeline sees it at ``hour``: the same item rows with that hour's
+        bias (``bias``: a buffer to use in its place, the graphed scorer's static one)."""
+        scale = self.hour_table()
+        return HourView(self, scale, self.hour_bias(hour) if bias is None else bias)
+
+
+class HourView:
+    """An ``ItemIndex`` at one hour of day: its ``p`` / ``p3`` / ``pmax`` / ``terms`` / ``ids`` /
+    ``dim`` (the item rows do not depend on the hour), the hour's ``bias`` and the query scale
+    table.  The collect, select and re-run code reads it like an index."""
+
+    def __init__(self, base: ItemIndex, scale: torch.Tensor, bias: torch.Tensor):
+        self.base, self.scale, self.bias = base, scale, bias
+        self.p, self.p3, self.pmax, self.terms = base.p, base.p3, base.pmax, base.terms
+        self.ids, self.dim = base.ids, base.dim
 
 
 def _param_version(model):
@@ -368,6 +496,9 @@ class _TopKRun:
         self.sbias = index.bias[::self.stride][:self.S].contiguous()
         e = lambda *sh, dt=torch.float32: torch.empty(*sh, dtype=dt, device=dev)  # noqa: E731
         self.uid = e(max(n, 1), dt=torch.int64)
+        # an index at an hour (HourView): the users' hours, read by ncf_score_queries_hour
+        self.hours = torch.zeros(max(n, 1), dtype=torch.int64, device=dev) \
+            if isinstance(index, HourView) else None
         self.s16 = s16 and self.S <= KTH_LDS_MAX
         # (rank j only where the sample leaves >= 8 k candidates expected: a small catalogue's
         # sample floor of 4096 items would otherwise put the j-th near the k-th item overall)
@@ -401,11 +532,18 @@ class _TopKRun:
         p, bias = idx.p, idx.bias
         I, D = p.shape
         table = model.mf_embedding_collection.embedding_bags["user_id"].weight
-        _lib.call("ncf_score_queries", ptr(self.uid), n, ptr(table), model.num_users,
-                  model.mf_embedding_dim,
-                  ptr(model.mf_norm.weight), ptr(model.mf_norm.bias), LN_EPS,
-                  ptr(model.mf_output.weight), ptr(model.final[0].weight), ptr(self.q),
-                  ptr(self.err), st)
+        if self.hours is not None:   # q_u (.) s_h, h = self.hours[u's row]
+            _lib.call("ncf_score_queries_hour", ptr(self.uid), ptr(self.hours), n, ptr(table),
+                      model.num_users, model.mf_embedding_dim,
+                      ptr(model.mf_norm.weight), ptr(model.mf_norm.bias), LN_EPS,
+                      ptr(model.mf_output.weight), ptr(model.final[0].weight), ptr(idx.scale),
+                      ptr(self.q), ptr(self.err), st)
+        else:
+            _lib.call("ncf_score_queries", ptr(self.uid), n, ptr(table), model.num_users,
+                      model.mf_embedding_dim,
+                      ptr(model.mf_norm.weight), ptr(model.mf_norm.bias), LN_EPS,
+                      ptr(model.mf_output.weight), ptr(model.final[0].weight), ptr(self.q),
+                      ptr(self.err), st)
         if self.s16:
             _lib.call("ncf_score_sample_split16", ptr(self.q), n, ptr(idx.p3), I, D, self.stride,
                       ptr(self.sbias), self.S, self.G, ptr(self.sample), st)
@@ -563,33 +701,118 @@ class _TopKRun:
         return self.scores, items
 
 
+def _check_hour(hour, n_users: int):
+    """The ``hour=`` argument before any launch: None, an int in [0, 24) (IndexError outside), or
+    an integer tensor with one hour per user (ValueError at another length), returned flat."""
+    if hour is None:
+        return None
+    if isinstance(hour, torch.Tensor) and hour.dim() > 0:
+        if hour.is_floating_point() or hour.dtype == torch.bool:
+            raise TypeError("hour must be an int or an integer tensor")
+        hour = hour.reshape(-1)
+        if hour.numel() != n_users:
+            raise ValueError(f"hour holds {hour.numel()} entries for {n_users} users "
+                             "(one hour per user, or one int)")
+        return hour
+    if isinstance(hour, (bool, float)) or \
+            (isinstance(hour, torch.Tensor) and hour.is_floating_point()):
+        raise TypeError("hour must be an int or an integer tensor")
+    hour = int(hour)
+    if not 0 <= hour < 24:
+        raise IndexError(f"hour {hour} is outside [0, 24)")
+    return hour
+
+
+def _one_hour(hour, n_users: int) -> int:
+    """``_check_hour`` for the graphed scorer, whose replay runs at one hour."""
+    hour = _check_hour(hour, n_users)
+    if isinstance(hour, torch.Tensor):
+        if hour.numel() == 0 or bool((hour != hour[0]).any()):
+            raise ValueError("GraphedScorer replays one hour per call (an int); users at "
+                             "several hours go through score_topk(hour=tensor)")
+        hour = _check_hour(int(hour[0]), n_users)
+    return hour
+
+
+def group_by_hour(hours: torch.Tensor):
+    """``[(hour, positions)]`` over the distinct values of a 1-D integer tensor, hours ascending,
+    every group's positions (int64, on the tensor's device) in the caller's order."""
+    hours = hours.reshape(-1)
+    if hours.numel() == 0:
+        return []
+    order = torch.argsort(hours, stable=True)
+    uniq, counts = torch.unique_consecutive(hours[order], return_counts=True)
+    return list(zip(uniq.tolist(), torch.split(order, counts.tolist())))
+
+
+def _topk_eager(model, uid, k, idx, cap, exclude, hours=None):
+    """One eager pipeline run of ``uid`` over ``idx`` (an ItemIndex, or a HourView with the
+    users' ``hours``: an int, or a tensor the kernel range-checks)."""
+    n = uid.numel()
+    run = _TopKRun(idx, n, k, cap, exclude=exclude)
+    if n == 0:
+        return run.result()
+    st = _lib.stream_ptr(uid.device)
+    run.uid[:n].copy_(uid)
+    if run.hours is not None:
+        if isinstance(hours, torch.Tensor):
+            run.hours[:n].copy_(hours)
+        else:
+            run.hours.fill_(hours)
+    run.launch(model, st)
+    run.redo_overflow(st)
+    err = int(run.err.item())
+    if err & 1:
+        raise IndexError("score_topk: user id out of range of the embedding table")
+    if err & 2:
+        raise IndexError("score_topk: hour outside [0, 24)")
+    return run.result()
+
+
 def score_topk(model, user_ids: torch.Tensor, k: int = 10, index: Optional[ItemIndex] = None,
                cap: int = 8192, *,
-               exclude: Optional[SeenItems] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               exclude: Optional[SeenItems] = None, hour=None,
+               projection=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k (probability, item id) per user over all items, as
     ``forward_simple(user, all_items)`` + ``nlargest(k)`` would rank them.  Returns
     ``(scores [n, k] fp32, items [n, k] int64)``.  ``exclude``: every user's seen items
     (``SeenItems``, on the index's device): the top k of the others instead, exact by the same
-    order; a user with fewer than k unseen items gets trailing ``(0.0, -1)`` slots."""
+    order; a user with fewer than k unseen items gets trailing ``(0.0, -1)`` slots.
+    ``hour``: rank as ``forward_simple(user, all_items, hour)`` does, at one int hour or at one
+    hour per user (an integer tensor: the users are grouped by hour, one run per distinct hour,
+    the results back in the caller's order).  ``projection``: the hour path's ``nn.Linear(T, D)``
+    or ``(weight, bias)`` for the index this call builds (an ``index`` brings its own)."""
     _check_exclude(exclude, model.num_users, model.num_products)
+    hour = _check_hour(hour, user_ids.numel())
     if index is None:
-        index = ItemIndex(model)
-    elif not index.valid_for(model):   # parameters changed since the index was built
-        index = ItemIndex(model, items=index.ids)
+        index = ItemIndex(model, projection=projection)
+    else:
+        if projection is not None and not index.owns_projection(projection):
+            raise ValueError("score_topk: index was built with another projection; pass the "
+                             "projection to ItemIndex and leave it out here")
+        if not index.valid_for(model):   # parameters changed since the index was built
+            index = ItemIndex(model, items=index.ids, projection=index.projection)
     dev = index.p.device
     _check_exclude(exclude, model.num_users, model.num_products, dev)
-    uid = user_ids.to(device=dev, dtype=torch.int64).contiguous()
+    uid = user_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
     n = uid.numel()
-    run = _TopKRun(index, n, k, cap, exclude=exclude)
-    if n == 0:
-        return run.result()
-    st = _lib.stream_ptr(dev)
-    run.uid[:n].copy_(uid)
-    run.launch(model, st)
-    run.redo_overflow(st)
-    if int(run.err.item()):
-        raise IndexError("score_topk: user id out of range of the embedding table")
-    return run.result()
+    if hour is None or n == 0:
+        return _topk_eager(model, uid, k, index, cap, exclude)
+    if not isinstance(hour, torch.Tensor):
+        return _topk_eager(model, uid, k, index.at_hour(hour), cap, exclude, hour)
+    hour = hour.to(device=dev, dtype=torch.int64)
+    groups = group_by_hour(hour)
+    # (an hour out of range: its group runs at hour 0 and the kernel flags it, which raises)
+    view = lambda h: index.at_hour(h if 0 <= h < 24 else 0)   # noqa: E731
+    if len(groups) == 1:
+        return _topk_eager(model, uid, k, view(groups[0][0]), cap, exclude, hour)
+    scores = torch.empty(n, k, device=dev)
+    items = torch.empty(n, k, dtype=torch.int64, device=dev)
+    for h, pos in groups:
+        s, i = _topk_eager(model, uid[pos], k, view(h), cap, exclude, hour[pos])
+        scores[pos] = s
+        items[pos] = i
+    return scores, items
 
 
 class GraphedScorer:
@@ -610,25 +833,42 @@ class GraphedScorer:
     ``exclude`` (``SeenItems``) as in ``score_topk``.  The lists are looked up by user id inside
     the graph, so it holds the CSR's two pointers only and any users can be replayed; users whose
     seen items reach into their top k take the eager re-run after the replay.
+
+    ``hour`` (an int) captures the hour pipeline of ``score_topk(hour=)``; a call then takes
+    ``scorer(user_ids, hour=h)``, one int hour per call (default: the last one).  Another hour
+    overwrites the scorer's bias buffers in place and replays the same graph.  ``projection``
+    as in ``score_topk``.
     """
 
     def __init__(self, model, n_users: int, k: int = 10, index: Optional[ItemIndex] = None,
-                 cap: int = 8192, *, exclude: Optional[SeenItems] = None):
+                 cap: int = 8192, *, exclude: Optional[SeenItems] = None, hour=None,
+                 projection=None):
         self.model, self.n, self.k, self.cap = model, int(n_users), int(k), cap
         if self.n < 1:
             raise ValueError("GraphedScorer needs n_users >= 1")
         _check_exclude(exclude, model.num_users, model.num_products)
         self.exclude = exclude
+        # the hour the static buffers hold (None: the hour=None pipeline, captured without them)
+        self.hour = None if hour is None else _one_hour(hour, self.n)
+        if index is not None and projection is not None and not index.owns_projection(projection):
+            raise ValueError("GraphedScorer: index was built with another projection")
         self.index = index if index is not None and index.valid_for(model) else ItemIndex(
-            model, items=None if index is None else index.ids)
+            model, items=None if index is None else index.ids,
+            projection=projection if index is None else index.projection)
         self._capture()
 
     def _capture(self):
         idx = self.index
         dev = idx.p.device
         _check_exclude(self.exclude, self.model.num_users, self.model.num_products, dev)
+        if self.hour is not None:
+            # the captured kernels read a bias buffer of the scorer's own (and the run's sbias,
+            # its sample's rows): _set_hour overwrites both in place, no re-capture per hour
+            idx = idx.at_hour(self.hour, bias=idx.hour_bias(self.hour).clone())
         self.run = run = _TopKRun(idx, self.n, self.k, self.cap, exclude=self.exclude)
         run.uid.zero_()
+        if self.hour is not None:
+            run.hours.fill_(self.hour)
         st = _lib.stream_ptr(dev)
         run.launch(self.model, st)           # warm-up: kernel attributes, lazy module loads
         torch.cuda.synchronize(dev)
@@ -639,17 +879,38 @@ class GraphedScorer:
             run.launch(self.model, _lib.stream_ptr(dev))
             self.flags = torch.stack([run.overflow[:self.n].amax(), run.err[0]])
             self.out = run.result()
-        self.version = idx.version
+        self.version = self.index.version
 
-    def __call__(self, user_ids: torch.Tensor,
-                 copy: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _set_hour(self, hour: int):
+        """Point the captured pipeline at ``hour``: the index's cached bias of that hour into
+        the static bias buffer and its sample rows into the run's sbias, the hour into the
+        per-user hour buffer (all in place)."""
+        run = self.run
+        view = run.index
+        view.bias.copy_(self.index.hour_bias(hour))
+        run.sbias.copy_(view.bias[::run.stride][:run.S])
+        run.hours.fill_(hour)
+        self.hour = hour
+
+    def __call__(self, user_ids: torch.Tensor, copy: bool = True, *,
+                 hour=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        uid = user_ids.reshape(-1)
+        if hour is not None:
+            if self.hour is None:
+                raise ValueError("this GraphedScorer was captured for hour=None; build it with "
+                                 "hour= to score at an hour")
+            hour = _one_hour(hour, uid.numel())
         if not self.index.valid_for(self.model):
-            self.index = ItemIndex(self.model, items=self.index.ids)
+            self.index = ItemIndex(self.model, items=self.index.ids,
+                                   projection=self.index.projection)
+            if hour is not None:
+                self.hour = hour
             self._capture()
         run = self.run
-        uid = user_ids.reshape(-1)
         if uid.numel() != self.n:
             raise ValueError(f"GraphedScorer was captured for {self.n} users, got {uid.numel()}")
+        if hour is not None and hour != self.hour:
+            self._set_hour(hour)
         run.uid.copy_(uid)
         run.err.zero_()
         self.graph.replay()
@@ -689,34 +950,42 @@ def merge_topk(cand_scores: torch.Tensor, cand_items: torch.Tensor, k: int):
 def sharded_score_topk(model, user_ids: torch.Tensor, k: int = 10,
                        index: Optional[ItemIndex] = None, group=None, cap: int = 8192,
                        local_topk=None, merge=None, graph: bool = False, *,
-                       exclude: Optional[SeenItems] = None):
+                       exclude: Optional[SeenItems] = None, hour=None, projection=None):
     """Item-sharded C5 scoring over ``torch.distributed``: rank r scores every
     queried user against ``shard_items(I, W, r)``, the ``[n, k]`` local lists are all-gathered
     (8 B per entry + id widening) and merged per user.  Every rank returns the global top-k.
     ``local_topk(user_ids, k) -> (scores, global ids)`` and ``merge`` default to the HIP path
     (they are parameters so the collective layout can be exercised on CPU ranks).  ``exclude``
     (``SeenItems``, global item ids, the same on every rank) as in ``score_topk``: each shard
-    leaves out the seen items it holds."""
+    leaves out the seen items it holds.  ``hour`` / ``projection`` as in ``score_topk`` (with
+    ``graph``: one int hour per call); each shard builds the hour's bias over its own items."""
     import torch.distributed as dist
     W = dist.get_world_size(group) if dist.is_initialized() else 1
     r = dist.get_rank(group) if dist.is_initialized() else 0
     if local_topk is None:
+        hour = _check_hour(hour, user_ids.numel())
+        if index is not None and projection is not None and \
+                not index.owns_projection(projection):
+            raise ValueError("sharded_score_topk: index was built with another projection")
         if index is None or not index.valid_for(model):
-            index = ItemIndex(model, items=shard_items(model.num_products, W, r))
+            index = ItemIndex(model, items=shard_items(model.num_products, W, r),
+                              projection=projection if index is None else index.projection)
         kk = min(k, index.p.shape[0])
 
         def local_topk(u, _k):
             if graph:   # the shard's pipeline as a captured hipGraph (cached on the index)
                 gs = index.__dict__.setdefault("_graphed", {})
-                # (a scorer keeps its SeenItems alive, so the id in the key stays its own)
-                key = (u.numel(), kk, cap) + (() if exclude is None else (id(exclude),))
+                # (a scorer keeps its SeenItems alive, so the id in the key stays its own; an
+                # hour scorer replays any hour, so the key holds only whether it is one)
+                key = (u.numel(), kk, cap) + (() if exclude is None else (id(exclude),)) + \
+                    (() if hour is None else ("hour",))
                 sc = gs.get(key)
                 if sc is None:
                     sc = gs[key] = GraphedScorer(model, u.numel(), kk, index, cap,
-                                                 exclude=exclude)
-                s, i = sc(u)
+                                                 exclude=exclude, hour=hour)
+                s, i = sc(u) if hour is None else sc(u, hour=hour)
             else:
-                s, i = score_topk(model, u, kk, index, cap, exclude=exclude)
+                s, i = score_topk(model, u, kk, index, cap, exclude=exclude, hour=hour)
             if kk < _k:   # a shard smaller than k: pad with empty slots
                 s = torch.cat([s, s.new_zeros(s.shape[0], _k - kk)], 1)
                 i = torch.cat([i, i.new_full((i.shape[0], _k - kk), -1)], 1)
