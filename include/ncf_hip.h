@@ -763,6 +763,26 @@ int ncf_score_select_rescored_excl(const int32_t* user_list, int64_t n_users,
 int ncf_score_merge(const float* cand_score, const int64_t* cand_item, int64_t n_users, int64_t L,
                     int K, float* out_score, int64_t* out_item, void* stream);
 
+/* ---- exact nearest-product search over the exported embeddings (api.py:63-73: the query the
+ * Tree-AH index of setup_tree_ah_endpoint.py:25-32 answers approximately; csrc/neighbors.hip) --
+ * similarity(q, i) = fp32 dot product of query q (divided by its L2 norm first when normalize
+ * != 0; a zero query stays zero) and row i of vectors [n_items, dim] (unit rows, so this is the
+ * cosine), in a fixed accumulation order (v_mfma_f32_32x32x2_f32).  The catalogue is cut into
+ * slabs of slab_items rows; one workgroup scans one slab for one block of up to 32 queries and
+ * writes, per query, the exact top min(K, matches) of its slab as a list of K (similarity, item
+ * position) ordered by similarity desc then position asc, unused slots (0, -1): part_* are
+ * [n_queries, n_slabs, K], the layout ncf_score_merge reads.  n_slabs >= ceil(n_items /
+ * slab_items); the slabs past the catalogue give empty lists (padding for a two-level merge).
+ * Filters, applied before the selection: item i is left out for query q when query_cat[q] >= 0
+ * and item_cat[i] != query_cat[q], or when i == query_skip[q].  item_cat / query_cat /
+ * query_skip may be NULL (query_cat needs item_cat).  A NaN similarity is never selected.
+ * 1 <= K <= 128; dim 16, 32, 64 or 128; n_items < 2^31; n_queries <= 32 * 65535; queries and
+ * vectors 16-byte aligned. */
+int ncf_nn_scan(const float* queries, int64_t n_queries, int normalize, const float* vectors,
+                int64_t n_items, int64_t dim, const int32_t* item_cat, const int32_t* query_cat,
+                const int64_t* query_skip, int64_t slab_items, int64_t n_slabs, int K,
+                float* part_sim, int64_t* part_item, void* stream);
+
 /* ---- a13: torch.optim.Adam step (trainer.py:71-75, :285) ----------------------------------
  * Dense-exact over a whole table via the slot map (every row decays every step).            */
 int ncf_adam_table(float* param, float* exp_avg, float* exp_avg_sq, int64_t rows, int64_t dim,

@@ -14,5 +14,6 @@ from .sparse import (EmbeddingBagCollection, EmbeddingBagConfig, JaggedTensor,  
 from .architecture import (AdvancedNCF, CategoryHierarchy, MultiHeadAttention,  # noqa: F401
                            TemporalEncoding)
 from .scoring import SeenItems  # noqa: F401
+from .neighbors import ProductSearch  # noqa: F401
 
 __version__ = "1.0.0"

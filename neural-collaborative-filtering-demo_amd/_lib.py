@@ -202,6 +202,7 @@ SIGNATURES = {
     "ncf_score_select_rescored_excl": (I32, [P, I64, P, P, I64, I32, P, P, P, I64, P, F32, P, P, P,
                                              P, P, P, I64, P, P, P, P]),
     "ncf_score_merge": (I32, [P, P, I64, I64, I32, P, P, P]),
+    "ncf_nn_scan": (I32, [P, I64, I32, P, I64, I64, P, P, P, I64, I64, I32, P, P, P]),
     "ncf_temporal_fwd": (I32, [P, P, P, P, I64, P, P, P, P, I64, I64, P, P, P]),
     "ncf_temporal_bwd": (I32, [P, P, P, I64, P, I64, P, P, P, P]),
 }

@@ -32,20 +32,13 @@
 //                             list of seen items (k_select<.., EX>), always with thr_check.
 // Tilings: see k_collect (fp32) and k_collect3 (split bf16) below.
 #include "ncf_common.h"
+#include "select_dev.h"   // fkey / fkey_inv, wave_lds_sync, bitonic_desc
 #include <algorithm>
 #include <type_traits>
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ uint32_t fkey(float f) {  // order-preserving float -> uint32
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 
 // ---- 1. queries: q = w0 * LN(U_mf[id]) (.) w_mf; L = D/4 lanes per row.  The rows are QD =
 // max(64, D) floats wide: a D < 64 row is zero-padded (the item index pads its rows the same way,
@@ -623,12 +616,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // B operands of tile t + 1 are read from LDS while tile t is multiplied.  Hits go to the wave's
 // own LDS slice (offsets from ballots, no atomics) and the wave writes its slice to the global
 // lists itself when it fills (no workgroup barrier).
-// LDS writes of this wave visible to its other lanes (LDS-only fence: no global cache traffic)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 // A wave's staged candidates written out grouped by user (k_collect3): per-user counts and
 // ranks (LDS atomics), a wave scan for the group offsets, ONE global counter atomic per user
@@ -985,24 +972,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
 }
 
 // ---- 4. per-user selection: bitonic sort (descending) of 64-bit keys (logit key | ~item)
-constexpr int kSelectMax = 8192;
-
-// in-LDS bitonic sort of n2 (a power of two) keys, descending; the whole block participates
-__device__ __forceinline__ void bitonic_desc(unsigned long long* keys, int n2) {
-  for (int size = 2; size <= n2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int j = threadIdx.x; j < n2; j += blockDim.x) {
-        const int p = j ^ stride;
-        if (p > j) {
-          const bool desc = (j & size) == 0;
-          const unsigned long long x = keys[j], y = keys[p];
-          if ((x < y) == desc) { keys[j] = y; keys[p] = x; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
+constexpr int kSelectMax = 8192;   // (bitonic_desc: select_dev.h)
 
 // Per user: the K best candidates without sorting the whole list.  The candidates' order keys
 // (fkey of the logit) go to LDS; a radix select over key - min (8-bit digits from the highest bit

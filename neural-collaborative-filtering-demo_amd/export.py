@@ -65,6 +65,31 @@ def write_embeddings_jsonl(out: Union[str, IO[str]], ids: Sequence[str],
     return len(ids)
 
 
+def read_embeddings_jsonl(src: Union[str, IO[str]]) -> Tuple[List[str], torch.Tensor]:
+    """The inverse of ``write_embeddings_jsonl``: ``(ids, embeddings [n, D] fp32 on the CPU)`` of
+    a JSONL file (a path or an open file), blank lines skipped; the floats come back as the bits
+    that were written (``json`` prints a double so that it reads back the same).  Rows of
+    differing width raise ``ValueError``."""
+    fh = open(src) if isinstance(src, str) else src
+    try:
+        ids, rows = [], []
+        for line in fh:
+            if not line.strip():
+                continue
+            rec = json.loads(line)
+            ids.append(str(rec["id"]))
+            rows.append(rec["embedding"])
+    finally:
+        if isinstance(src, str):
+            fh.close()
+    width = len(rows[0]) if rows else 0
+    if any(len(r) != width for r in rows):
+        raise ValueError("embeddings of differing width")
+    # (the writer printed each fp32 widened to a double: narrowing it again is exact)
+    emb = torch.tensor(rows, dtype=torch.float64).to(torch.float32).reshape(len(rows), width)
+    return ids, emb
+
+
 def distinct_products(rows: Iterable[Mapping], num_products: int) -> Tuple[List[str], List[int]]:
     """The reference's row filter (generate_embeddings.py:193-203): skip rows without a
     product_id and repeats; returns (product ids, table rows) in first-seen order."""
