@@ -137,6 +137,34 @@ int ncf_embedding_export(const int64_t* ids, int64_t n, const float* table, int6
                          int64_t dim, const float* ln_gamma, const float* ln_beta, float eps,
                          int l2_normalize, float* out, int* err_flag, void* stream);
 
+/* ---- pooled bags (torchrec EmbeddingBagCollection with any bag length; nn.EmbeddingBag) ----
+ * out[b, :] = scale_b * sum_{p in [offsets[b], offsets[b+1])} w_p * table[ids[p], :] for `bags`
+ * bags over ids[n_ids]; offsets int64[bags + 1], relative to ids; weights float[n_ids] or NULL
+ * (every w_p = 1); mode 0 = SUM (scale_b = 1), 1 = MEAN (scale_b = 1 / length_b).  The sum runs
+ * in position order, starting from the first term: an unweighted bag of one id is the bits of
+ * ncf_gather_rows without LayerNorm, in both modes.  An empty bag is a zero row.  dim 16, 32,
+ * 64, 128 or 256; fp32 table.  An id outside [0, rows) contributes nothing and sets bit 0x1 of
+ * *err_flag; a bag whose offsets decrease or leave [0, n_ids] sets bit 0x2 and is clamped into
+ * the range, so nothing is read out of bounds.  bags == 0 launches nothing.                  */
+int ncf_bag_pool_fwd(const int64_t* ids, int64_t n_ids, const int64_t* offsets, int64_t bags,
+                     const float* weights, const float* table, int64_t rows, int64_t dim,
+                     int mode, float* out, int* err_flag, void* stream);
+/* Backward of ncf_bag_pool_fwd for grad_out [bags, dim]: the dense gradient
+ *   grad_table[r, :] = sum_{p : ids[p] = r} scale_b(p) * w_p * grad_out[b(p), :]
+ * ([rows, dim], zero-filled here; rows never referenced stay zero) and, when grad_weights is not
+ * NULL (SUM only; needs table), grad_weights[p] = <grad_out[b(p), :], table[ids[p], :]>.  No
+ * float atomics: the ids are sorted stably (ncf_dedup_ids2 with an empty second list) and every
+ * unique id's terms are added in sorted-position order, in chunks of at most 16 whose partial
+ * sums are added in chunk order, so the result is a pure function of the input.  Ids out of
+ * range and positions no bag holds contribute nothing.  grad_table may be NULL when only
+ * grad_weights is wanted (no sort then); table may be NULL when grad_weights is.  workspace:
+ * ncf_bag_pool_bwd_workspace(n_ids, bags, dim) bytes.  n_ids < 2^30, rows <= 2^32.          */
+int64_t ncf_bag_pool_bwd_workspace(int64_t n_ids, int64_t bags, int64_t dim);
+int ncf_bag_pool_bwd(const int64_t* ids, int64_t n_ids, const int64_t* offsets, int64_t bags,
+                     const float* weights, const float* table, const float* grad_out,
+                     int64_t rows, int64_t dim, int mode, float* grad_table, float* grad_weights,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- dense layers: fp32 MFMA GEMM (v_mfma_f32_32x32x2_f32) --------------------------------
  * Replaces the addmm/mm of the attention projections (architecture.py:40-42, :57) and the MLP
  * tower Linear layers (:230-246) fwd and bwd.  C = act(A·B + bias); A(i,k) = a_trans ?

@@ -10,7 +10,7 @@ This directory's name (``neural-collaborative-filtering-demo_amd``) is not a Pyt
 """
 from ._lib import LIB_PATH, NCFLibraryError, load as load_library  # noqa: F401
 from .sparse import (EmbeddingBagCollection, EmbeddingBagConfig, JaggedTensor,  # noqa: F401
-                     KeyedJaggedTensor, PoolingType)
+                     KeyedJaggedTensor, PoolingType, pool_rows)
 from .architecture import (AdvancedNCF, CategoryHierarchy, MultiHeadAttention,  # noqa: F401
                            TemporalEncoding)
 from .scoring import SeenItems  # noqa: F401

@@ -57,6 +57,9 @@ SIGNATURES = {
     "ncf_gather_ln_gmf_bf16_fwd": (I32, [P, P, I64, P, P, P, P, I64, I64, I64, P, P, P, P, P, P,
                                          F32, I64, P, P, P, P, P, P, P]),
     "ncf_gather_rows": (I32, [P, I64, P, I64, I64, P, P, F32, P, P, P]),
+    "ncf_bag_pool_fwd": (I32, [P, I64, P, I64, P, P, I64, I64, I32, P, P, P]),
+    "ncf_bag_pool_bwd_workspace": (I64, [I64, I64, I64]),
+    "ncf_bag_pool_bwd": (I32, [P, I64, P, I64, P, P, P, I64, I64, I32, P, P, P, I64, P]),
     "ncf_gemm_f32": (I32, [I64, I64, I64, P, I64, I32, P, I64, I32, P, I64, P, I32, P]),
     "ncf_gemm_splitk_workspace": (I64, [I64, I64, I32]),
     "ncf_gemm_f32_splitk": (I32, [I64, I64, I64, P, I64, I32, P, I64, I32, P, I64, I32, P, I32,
