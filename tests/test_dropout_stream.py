@@ -111,15 +111,17 @@ def test_oracle_headroom_of_gpu_case(name):
     c = TD.CASES[name]
     D, H, M, B, p, steps = (c[k] for k in ("D", "H", "M", "B", "p", "steps"))
     seeds = TD.case_seeds(name, steps)
-    init = {k: v.detach().clone() for k, v in TD.make_model(D, H, M, p).state_dict().items()}
+    geo = TD.geo(c)
+    hid, tdim = geo["hid"], geo["tdim"]
+    init = {k: v.detach().clone() for k, v in TD.make_model(D, H, M, p, **geo).state_dict().items()}
     if c.get("table_dtype") == "bf16":
         init = TD.bf16_tables(init)
     batches = TD.make_batches(B, M, steps, c["data_seed"])
-    r64, _ = TD.oracle_run(init, batches, seeds, H, M, p, torch.float64)
-    r32, _ = TD.oracle_run(init, batches, seeds, H, M, p, torch.float32)
+    r64, _ = TD.oracle_run(init, batches, seeds, H, M, p, torch.float64, hid=hid, tdim=tdim)
+    r32, _ = TD.oracle_run(init, batches, seeds, H, M, p, torch.float32, hid=hid, tdim=tdim)
     for seed, a, b in zip(seeds, r64, r32):
         if p > 0:
-            m = S.step_masks(seed, B, H, M, TD.HID, p)
+            m = S.step_masks(seed, B, H, M, hid, p)
             for x in [m["attn"]] + m["mlp"]:
                 assert abs(float((x > 0).mean()) - (1 - p)) < 4 * (p * (1 - p) / x.size) ** 0.5
         assert (a["prob"] - b["prob"].double()).abs().max().item() < 5e-6 / 4

@@ -16,6 +16,11 @@ each case below): the fp32 oracle stays within a quarter of every tolerance.  Re
 decide a comparison: in the float64 oracle no tower pre-activation is closer to 0 than 4 x the
 largest fp32-vs-float64 pre-activation difference measured for that case (``pre``, asserted).
 
+A case may carry its own tower widths, temporal dim and MF table width (``hid``, ``tdim``,
+``Dm``): the ``g_*`` cases run the per-layer path at the edges of the geometries the engine
+accepts (D 16 to 256, head dim 8 and 64, M up to 64, widths 16 to 1024, one to four layers, the
+two collections at different widths), and one test pins what lies just outside as refused.
+
 Also here: the standalone MultiHeadAttention in training mode (attention.hip's LMAX 8 and 64
 forms, masked and not) against O.mha(..., drop_mask=...) in float64.
 """
@@ -119,9 +124,48 @@ CASES["bf16mm_e2e_80"] = _mm(64, 4, 5, 37, 0.2, "fused_80", {"SMALL_TILE_GROUPS"
 CASES["bf16mm_e2e_d128"] = _mm(128, 8, 6, 19, 0.2, "block", {}, 5)
 
 
-def make_model(D, H, M, p):
+# The per-layer path at the edges of the geometries the engine accepts, under the default switches
+# (form "generic": projection GEMMs or the attention block, attention.hip's core, one GEMM + row
+# launch per tower layer, ncf_head_fwd/_bwd, the grouped weight gradients), 2 host-seeded steps each.
+def _generic(D, H, M, B, p, hid, data_seed, pre, attn_block=False, **kw):
+    return _case(D, H, M, B, p, 2, "host", "generic", {}, data_seed, pre, hid=hid,
+                 attn_block=attn_block, **kw)
+
+
+CASES.update({
+    # every narrowest form (D = 16, head dim 8, W = 16), a one-layer tower
+    # CPU: |dprob| 6.9e-8, |dloss| 3.7e-8, gradient at 0.0064 of its tolerance; nearest 1.51e-4
+    "g_d16": _generic(16, 2, 2, 20, 0.2, [16], 2, 6.78e-8),
+    # head dim 8 with M = 9: attention.hip's LMAX 64 core; W = 512: two float4 chunks per lane.
+    # 10 of the data seeds 1..60 are admitted (the others leave a pre-activation within 4 x pre
+    # of 0).  CPU: 1.09e-7, 5.8e-8, 0.024; nearest 1.47e-5
+    "g_d32_m9": _generic(32, 4, 9, 6, 0.2, [512, 32], 50, 9.61e-7),
+    # W = 1024 (four chunks), the head at 256 / 256, D = 256 gather, segment reduce and Adam.
+    # Shrunk from B = 8: 24 rows x 1280 pre-activations, fp32 differences near 1e-5 (K = 1024 on
+    # LayerNorm'd rows), and none of the data seeds 1..60 at B = 8 or 1..150 at B = 4 keeps every
+    # pre-activation 4 x pre away from 0; at B = 3 seed 3 of 1..100 does (B = 2: seed 33 of 1..40).
+    # CPU: 5.9e-8, 4.3e-8, 0.064; nearest 3.52e-5
+    "g_d256": _generic(256, 4, 3, 3, 0.2, [1024, 256], 3, 5.10e-6),
+    # M = 64 with B = 3, one head of 64, four layers, ncf_gemm_rows (64,128) / (128,128) / (128,64),
+    # last width 16.  CPU: 8.2e-8, 6.8e-8, 0.012; nearest 2.84e-4
+    "g_d64_m64": _generic(64, 1, 64, 3, 0.0, [128, 128, 64, 16], 4, 7.51e-7),
+    # mf_embedding_dim 256 beside mlp_embedding_dim 32: the two collections at their own widths
+    # CPU: 8.2e-8, 7.5e-8, 0.011; nearest 4.70e-5
+    "g_split": _generic(32, 2, 5, 10, 0.2, [64, 32], 5, 7.27e-7, Dm=256),
+    # the attention block feeding the per-layer tower.  CPU: 1.09e-7, 9.8e-8, 0.089; nearest 1.07e-5
+    "g_block_tower": _generic(64, 8, 3, 12, 0.2, [128, 64], 5, 1.27e-6, attn_block=True),
+})
+
+
+def geo(c):
+    """A case's tower widths, temporal dim and MF table width (0: the MLP tables' D); the
+    defaults are what every case had before the generic ones."""
+    return dict(hid=list(c.get("hid", HID)), tdim=c.get("tdim", TDIM), Dm=c.get("Dm", 0))
+
+
+def make_model(D, H, M, p, hid=HID, tdim=TDIM, Dm=0):
     torch.manual_seed(INIT_SEED)
-    return ncf.AdvancedNCF(U, I, 5, 24, D, D, TDIM, HID, H, p, M - 1)
+    return ncf.AdvancedNCF(U, I, 5, 24, Dm or D, D, tdim, list(hid), H, p, M - 1)
 
 
 def make_batches(B, M, steps, data_seed):
@@ -146,8 +190,8 @@ def host_seed(k):
     return s
 
 
-def torch_masks(seed, B, H, M, p, dtype=torch.float64):
-    m = S.step_masks(seed, B, H, M, HID, p)
+def torch_masks(seed, B, H, M, p, dtype=torch.float64, hid=HID):
+    m = S.step_masks(seed, B, H, M, hid, p)
     return {"attn": torch.from_numpy(m["attn"]).to(dtype),
             "mlp": [torch.from_numpy(x).to(dtype) for x in m["mlp"]]}
 
@@ -157,7 +201,7 @@ def cast_state(sd, dtype):
             for k, v in sd.items()}
 
 
-def tower_preacts(p, u, i, M, H, masks):
+def tower_preacts(p, u, i, M, H, masks, hid=HID, tdim=TDIM):
     """The tower's pre-activations (the Linear outputs the ReLUs see) of the oracle's training
     forward, from the oracle's own pieces."""
     n = u.numel()
@@ -165,9 +209,9 @@ def tower_preacts(p, u, i, M, H, masks):
     xu = O.layer_norm(p[O.K_MLP_U][u], g, b).view(n // M, M, -1)
     xi = O.layer_norm(p[O.K_MLP_I][i], g, b).view(n // M, M, -1)
     att = O.mha(p, O.ATT, xu, xi, xi, H, masks["attn"]).reshape(n, -1)
-    x = torch.cat([att, torch.zeros(n, TDIM, dtype=att.dtype)], 1)
+    x = torch.cat([att, torch.zeros(n, tdim, dtype=att.dtype)], 1)
     out = []
-    for l in range(len(HID)):
+    for l in range(len(hid)):
         z = O.linear(x, p[f"mlp.{4 * l}.weight"], p[f"mlp.{4 * l}.bias"])
         out.append(z)
         x = O.layer_norm(torch.relu(z), p[f"mlp.{4 * l + 2}.weight"], p[f"mlp.{4 * l + 2}.bias"])
@@ -175,7 +219,8 @@ def tower_preacts(p, u, i, M, H, masks):
     return out
 
 
-def oracle_run(init, batches, seeds, H, M, p, dtype=torch.float64, linear=O.linear):
+def oracle_run(init, batches, seeds, H, M, p, dtype=torch.float64, linear=O.linear, hid=HID,
+               tdim=TDIM):
     """The oracle's trajectory over ``batches`` with the masks of ``seeds`` (one per step), on
     one host thread (test_gpu_fullsize: torch's threaded CPU reductions do not fix their order).
     Per step: prob, loss, grads, the parameters before the step, the pre-activations.
@@ -187,12 +232,12 @@ def oracle_run(init, batches, seeds, H, M, p, dtype=torch.float64, linear=O.line
         opt = O.AdamState(lr=LR, weight_decay=WD)
         rec = []
         for (u, i, t), seed in zip(batches, seeds):
-            masks = torch_masks(seed, u.numel() // M, H, M, p, dtype)
+            masks = torch_masks(seed, u.numel() // M, H, M, p, dtype, hid)
             before = {k: v.clone() for k, v in ref.items()}
             with torch.no_grad():
-                pre = tower_preacts(ref, u, i, M, H, masks)
+                pre = tower_preacts(ref, u, i, M, H, masks, hid, tdim)
             prob, loss, grads = O.train_step(ref, opt, u, i, t.to(dtype), negative_samples=M - 1,
-                                             num_heads=H, temporal_dim=TDIM, n_layers=len(HID),
+                                             num_heads=H, temporal_dim=tdim, n_layers=len(hid),
                                              dropout_masks=masks, linear=linear)
             rec.append(dict(prob=prob, loss=loss, grads=grads, before=before, pre=pre))
         return rec, ref
@@ -206,7 +251,7 @@ def case_seeds(name, steps):
     under the clock the base seed is the draw that follows the model's construction."""
     c = CASES[name]
     if c["kind"] == "clock":
-        make_model(c["D"], c["H"], c["M"], c["p"])
+        make_model(c["D"], c["H"], c["M"], c["p"], **geo(c))
         base = int(torch.randint(0, 2 ** 62, (1,)).item())
         return [S.clock_seed(base, s) for s in range(steps)]
     if c["kind"] == "reference":
@@ -230,16 +275,25 @@ def _check_form(name, eng, D, H, M, B):
     theirs."""
     import ncf_amd.engine as E
     sw, form = CASES[name]["sw"], CASES[name]["form"]
-    fused_one_launch = eng.attn_tower_step(D, H, M, HID)
+    hid = geo(CASES[name])["hid"]
+    fused_one_launch = eng.attn_tower_step(D, H, M, hid)
+    if form == "generic":
+        # under the default switches: the per-layer tower, behind the attention block or the
+        # projection GEMMs + attention.hip core as the case states
+        assert sw == {} and not eng.mlp_fused(D, hid) and not fused_one_launch
+        assert eng.attn_block(D, H, M) == CASES[name]["attn_block"]
+        assert eng.model.mlp_hidden_dims == hid and (eng.model.mf_embedding_dim != D) == bool(
+            geo(CASES[name])["Dm"])
+        return
     if form in ("fused_small", "fused_80"):
         assert fused_one_launch
         assert eng._tiles(B) == ("" if form == "fused_80" else "_small")
     elif form == "unfused":
-        assert not eng.attn_block(D, H, M) and not eng.mlp_fused(D, HID)
+        assert not eng.attn_block(D, H, M) and not eng.mlp_fused(D, hid)
         assert not eng.mlp_fused_wgrad() and not fused_one_launch
     else:
         assert form == "block"
-        assert eng.attn_block(D, H, M) and eng.mlp_fused(D, HID) and not fused_one_launch
+        assert eng.attn_block(D, H, M) and eng.mlp_fused(D, hid) and not fused_one_launch
         assert eng.attn_rc(D, H, M) == sw.get("ATTN_RC", False)
     assert E.TOWER_SPLIT is False
     assert eng._tower_entry("ncf_mlp_fwd", True) == ("ncf_mlp_fwd" if "BF16_MM" in sw
@@ -272,7 +326,7 @@ def gpu_run(name, monkeypatch, table_dtype=torch.float32, tower=False):
     c = CASES[name]
     D, H, M, B, p, steps, kind = (c[k] for k in ("D", "H", "M", "B", "p", "steps", "kind"))
     _set_switches(monkeypatch, c["sw"])
-    m = make_model(D, H, M, p)
+    m = make_model(D, H, M, p, **geo(c))
     init = {k: v.detach().clone() for k, v in m.state_dict().items()}
     m = m.to(DEV)
     eng = m.engine
@@ -340,16 +394,17 @@ def compare(name, init, batches, rec, final, params=True):
     """GPU records against the float64 oracle with the masks of each step's seed."""
     c = CASES[name]
     D, H, M, B, p = (c[k] for k in ("D", "H", "M", "B", "p"))
+    hid, tdim = geo(c)["hid"], geo(c)["tdim"]
     seeds = [r["seed"] for r in rec]
     assert len(set(seeds)) == len(seeds)
     if p == 0:      # (every keep-scale is 1: the dropout-off leg of the bf16-table cases)
-        assert all(float(x.min()) == 1.0 for x in S.step_masks(seeds[0], B, H, M, HID, p)["mlp"])
-    ora, ref = oracle_run(init, batches, seeds, H, M, p)
+        assert all(float(x.min()) == 1.0 for x in S.step_masks(seeds[0], B, H, M, hid, p)["mlp"])
+    ora, ref = oracle_run(init, batches, seeds, H, M, p, hid=hid, tdim=tdim)
     worst = dict(prob=0.0, loss=0.0, grad=0.0)
     zones = {}
     prev = None
     for s, (g, o, (u, i, t)) in enumerate(zip(rec, ora, batches)):
-        masks = S.step_masks(g["seed"], B, H, M, HID, p)
+        masks = S.step_masks(g["seed"], B, H, M, hid, p)
         # not vacuous: the masks drop about p of their elements, and differ from step to step
         for x in ([masks["attn"]] + masks["mlp"]) if p > 0 else []:
             keep = float((x > 0).mean())
@@ -383,10 +438,10 @@ def compare(name, init, batches, rec, final, params=True):
             zones.setdefault(k, []).append(zone_from_grads(v.numpy(), o["before"][k].numpy(), WD))
         if s == 0 and p > 0:
             # the masks of another seed are another function: the comparison can tell
-            other = torch_masks(g["seed"] + 1, B, H, M, p)
+            other = torch_masks(g["seed"] + 1, B, H, M, p, hid=hid)
             po = O.forward(cast_state(init, torch.float64), u, i, training=True,
-                           negative_samples=M - 1, num_heads=H, temporal_dim=TDIM,
-                           n_layers=len(HID), dropout_masks=other)
+                           negative_samples=M - 1, num_heads=H, temporal_dim=tdim,
+                           n_layers=len(hid), dropout_masks=other)
             assert (gprob - po).abs().max().item() > 1e-3
     print(f"{name}: worst |dprob| {worst['prob']:.3g} |dloss| {worst['loss']:.3g} "
           f"gradient at {worst['grad']:.3g} of its tolerance")
@@ -402,6 +457,40 @@ def test_train_step_with_dropout_vs_float64_oracle(monkeypatch, name):
     compare(name, init, batches, rec, final)
     # the seeds the CPU-side measurements were taken with (tests/test_dropout_stream.py)
     assert [r["seed"] for r in rec] == case_seeds(name, len(rec))
+
+
+def test_geometries_outside_the_accepted_family_are_refused():
+    """The edge of the family: D = 48, a tower width of 96 and head dim 4 are refused by name on
+    the first training forward (argument checks, before the refusing entry point launches
+    anything); a last width of 512 evaluates (ncf_head_fwd loops over any width) and is refused
+    by ncf_head_bwd's size check when trained."""
+    from ncf_amd.trainer import FusedTrainStep
+    u, i, t = make_batches(6, 2, 1, 3)[0]
+
+    def first_forward(D, H, hid):
+        m = make_model(D, H, 2, 0.0, hid=hid).to(DEV)
+        m.engine.forward(u.to(DEV), i.to(DEV), 2, True, 0.0, 0)
+
+    for args, msg in (((48, 4, HID), r"unsupported embedding dim 48 \(16/32/64/128/256\)"),
+                      ((64, 4, [96]), r"MLP width 96 unsupported \(powers of two 16\.\.1024\)"),
+                      ((16, 4, [16]), r"head dim 4 unsupported \(8/16/32/64\)")):
+        with pytest.raises((RuntimeError, ValueError), match=msg):
+            first_forward(*args)
+        torch.cuda.synchronize()
+    hid = [64, 512]
+    m = make_model(64, 4, 2, 0.0, hid=hid)
+    init = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    m = m.to(DEV).eval()
+    assert not m.engine.mlp_fused(64, hid)
+    with torch.no_grad():
+        prob = m(_kjt(u, i)).cpu().double().reshape(-1)
+    want = O.forward(cast_state(init, torch.float64), u, i, training=False, negative_samples=0,
+                     num_heads=4, temporal_dim=TDIM, n_layers=len(hid)).reshape(-1)
+    assert (prob - want).abs().max().item() < 5e-6
+    step = FusedTrainStep(m.train(), lr=LR, weight_decay=WD, deferred=False)
+    with pytest.raises(ValueError, match=r"ncf_head_bwd: bad size \(width, dim <= 256\)"):
+        step(u.to(DEV), i.to(DEV), t.to(DEV))
+    torch.cuda.synchronize()
 
 
 # ----------------------------------------------------------------------------- the stream itself
