@@ -1001,6 +1001,25 @@ int ncf_adam_pairs_catchup_lock_clock(const ncf_table_pair* pairs, int npairs, i
                                       int32_t lock, const ncf_step_clock* clock,
                                       const float* step_table, double beta1, double beta2,
                                       double eps, double weight_decay, void* stream);
+/* ncf_reduce_batch(list, scratch, scratch_floats, stream) and
+ * ncf_adam_pairs_catchup_lock_clock(pairs, ..., lock = 0, ..., stream) with the catch-up inside
+ * the first launch group's stage-1 launch (one grid holding both kinds of 256-thread blocks):
+ * the tail of FusedTrainStep, where the late catch-up of the next batch's rows ran on a side
+ * stream beside the reductions and cost the step two cross-queue event hops.  The same device
+ * code as the two calls and disjoint memory: the same bits.  Further launch groups (more than
+ * 24 descriptors) and stage 2 are ncf_reduce_batch's.  An empty list launches the plain
+ * catch-up; max_n <= 0 is ncf_reduce_batch; both: nothing.  (The reference's backward + Adam.step,
+ * src/model/trainer.py:282-285, give the same values.)
+ * ncf_reduce_catchup_set_order: which kind of block takes the low block indices of the fused
+ * launch and dispatches first (0 the reduce, the default; 1 the catch-up; 2 the two
+ * interleaved; < 0 queries); returns the previous setting.  An A/B knob: same bits. */
+int64_t ncf_reduce_catchup_set_order(int64_t order);
+int ncf_reduce_batch_catchup(const ncf_reduce_list* list, float* scratch, int64_t scratch_floats,
+                             const ncf_table_pair* pairs, int npairs, int64_t dim,
+                             const uint32_t* count, int64_t max_n, int32_t target_rel,
+                             const ncf_step_clock* clock, const float* step_table,
+                             double beta1, double beta2, double eps, double weight_decay,
+                             void* stream);
 /* The catch-up of the rows named by RAW id lists (ids0 for pairs[0], ids1 for pairs[1], n
  * occurrences each, duplicates allowed): the first occurrence of a row to raise its stamp to the
  * target (atomicMax) replays it, the others skip: the same rows, bit-identical, with no dedup

@@ -175,6 +175,9 @@ SIGNATURES = {
     "ncf_adam_pairs_catchup_clock": (I32, [P, I32, I64, P, I64, I32, P, P, F64, F64, F64, F64, P]),
     "ncf_adam_pairs_catchup_lock_clock": (I32, [P, I32, I64, P, I64, I32, I32, P, P, F64, F64, F64,
                                                 F64, P]),
+    "ncf_reduce_catchup_set_order": (I64, [I64]),
+    "ncf_reduce_batch_catchup": (I32, [P, P, I64, P, I32, I64, P, I64, I32, P, P, F64, F64, F64,
+                                       F64, P]),
     "ncf_adam_pairs_catchup_claim_clock": (I32, [P, I32, I64, P, P, I64, I32, P, P, F64, F64, F64,
                                                  F64, P]),
     "ncf_adam_pairs_apply_gsum_clock": (I32, [P, I32, I64, P, I64, I32, P, P, P, I32, P, P, F64,

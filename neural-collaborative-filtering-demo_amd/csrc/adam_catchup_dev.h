@@ -1,0 +1,206 @@
+// The deferred table Adam's catch-up of listed rows, as device code: the replay of the
+// zero-gradient steps a row owes (catch_up_row) and the body of the both-kinds catch-up
+// (pairs_catchup_body).  One definition for every kernel that replays rows: the catch-up, sweep
+// and claim kernels of adam.hip and the fused tail launch of reduce.hip (k_reduce1_catchup) take
+// the same arithmetic in the same order, so every schedule gives the same bits.
+#pragma once
+#include "ncf_common.h"
+#include "adam_math.h"
+
+namespace ncf_adam {
+namespace {
+
+// ---- deferred dense-exact schedule -------------------------------------------------------
+// A row that receives no gradient at step s still takes the step with g = 0 (weight decay only).
+// Instead of streaming every untouched row every step, rows carry stamp[row] = the last step
+// their (p, m, v) reflect; before a row is READ it is caught up by replaying the missing
+// zero-gradient steps s = stamp+1 .. target with that step's scalars (step table, 4 floats per
+// step: [4s] = -lr/(1-b1^s), [4s+1] = 1/sqrt(1-b2^s) for the gradient step adam1, [4s+2] / [4s+3]
+// = ra / rb for the zero-gradient step adam0), element by element, with the very same adam0
+// arithmetic as the dense sweep's untouched rows.
+// Results are bit-identical to the dense sweep; the cost moves from HBM traffic to VALU work.
+struct TablePtrs {
+  float *p0, *m0, *v0, *p1, *m1, *v1;  // two tables sharing the row index space (GMF + MLP)
+  const float *G0, *G1;                 // compact gradients (apply only)
+};
+
+// Replay layout: lane = column.  One row (of both tables of a pair) per wave when D >= 64
+// (EPL = D/64 columns per lane, stride 64), 64/D rows per wave when D < 64.  With one row per
+// wave the replay bounds (from, to) are wave-uniform: the step loop is scalar, the per-step
+// scalars come through the scalar cache, and no lane idles on another row's longer catch-up.
+template <int D>
+struct Replay {
+  static constexpr int LPR = D < 64 ? D : 64;   // lanes per row
+  static constexpr int EPL = D / LPR;           // columns per lane
+};
+
+// The replay of zero-gradient steps from+1 .. to on EPL columns of one (pair of) table row(s).
+// With wave-uniform bounds (one row per wave) the per-step scalars are scalar loads; they are
+// fetched 8 steps (16 floats) at a time, one chunk AHEAD of the steps that use them, so the
+// scalar-load latency hides behind 8 steps of VALU work instead of stalling every step (the
+// step table is padded >= 4096 steps past any target, deferred.py _ensure).  Same adam1 calls in
+// the same order: results are bit-identical to the step-by-step loop.
+template <int EPL, bool PAIR, bool BF = false>
+__device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, float* p1,
+                                               float* m1, float* v1, int32_t from, int32_t to,
+                                               const float* __restrict__ table,
+                                               const AdamScalars& s) {
+  constexpr int C = 8;                 // steps per chunk
+  int32_t q = from + 1;
+  float sc[2 * C];
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    sc[2 * k] = table[4 * (q + k) + 2];
+    sc[2 * k + 1] = table[4 * (q + k) + 3];
+  }
+  while (q + C - 1 <= to) {
+    float nx[2 * C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+      nx[2 * k] = table[4 * (q + C + k) + 2];
+      nx[2 * k + 1] = table[4 * (q + C + k) + 3];
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ahead of this chunk's steps
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+#pragma unroll
+      for (int j = 0; j < EPL; ++j) {
+        adam0(p0[j], m0[j], v0[j], sc[2 * k], sc[2 * k + 1], s);
+        if (BF) p0[j] = ncf_round_bf16(p0[j]);   // bf16 tables: stored (rounded) every step
+        if (PAIR) adam0(p1[j], m1[j], v1[j], sc[2 * k], sc[2 * k + 1], s);
+        if (PAIR && BF) p1[j] = ncf_round_bf16(p1[j]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 2 * C; ++k) sc[k] = nx[k];
+    q += C;
+  }
+#pragma unroll
+  for (int k = 0; k < C - 1; ++k) {    // the last to - q + 1 < C steps
+    if (q + k > to) break;
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) {
+      adam0(p0[j], m0[j], v0[j], sc[2 * k], sc[2 * k + 1], s);
+      if (BF) p0[j] = ncf_round_bf16(p0[j]);
+      if (PAIR) adam0(p1[j], m1[j], v1[j], sc[2 * k], sc[2 * k + 1], s);
+      if (PAIR && BF) p1[j] = ncf_round_bf16(p1[j]);
+    }
+  }
+}
+
+template <int D, bool BF = false>
+__device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, int sub, int32_t from,
+                                             int32_t to, const float* __restrict__ table,
+                                             const AdamScalars& s) {
+  constexpr int EPL = Replay<D>::EPL, LPR = Replay<D>::LPR;
+  if (Replay<D>::LPR == 64) {   // the whole wave holds this row: make the bounds scalar
+    from = __builtin_amdgcn_readfirstlane(from);
+    to = __builtin_amdgcn_readfirstlane(to);
+  }
+  if (from >= to) return;
+  const int64_t o = row * D + sub;
+  float p0[EPL], m0[EPL], v0[EPL], p1[EPL], m1[EPL], v1[EPL];
+#pragma unroll
+  for (int j = 0; j < EPL; ++j) {
+    p0[j] = ldp<BF>(t.p0, o + j * LPR); m0[j] = t.m0[o + j * LPR]; v0[j] = t.v0[o + j * LPR];
+  }
+  if (t.p1) {
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) {
+      p1[j] = ldp<BF>(t.p1, o + j * LPR); m1[j] = t.m1[o + j * LPR]; v1[j] = t.v1[o + j * LPR];
+    }
+    if (Replay<D>::LPR == 64) {
+      replay_uniform<EPL, true, BF>(p0, m0, v0, p1, m1, v1, from, to, table, s);
+    } else {
+#pragma unroll 2
+      for (int32_t q = from + 1; q <= to; ++q) {
+        const float ra = table[4 * q + 2], rb = table[4 * q + 3];
+#pragma unroll
+        for (int j = 0; j < EPL; ++j) {
+          adam0(p0[j], m0[j], v0[j], ra, rb, s);
+          adam0(p1[j], m1[j], v1[j], ra, rb, s);
+          if (BF) { p0[j] = ncf_round_bf16(p0[j]); p1[j] = ncf_round_bf16(p1[j]); }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) {
+      stp<BF>(t.p1, o + j * LPR, p1[j]); t.m1[o + j * LPR] = m1[j]; t.v1[o + j * LPR] = v1[j];
+    }
+  } else if (Replay<D>::LPR == 64) {
+    replay_uniform<EPL, false, BF>(p0, m0, v0, p1, m1, v1, from, to, table, s);
+  } else {
+#pragma unroll 2
+    for (int32_t q = from + 1; q <= to; ++q) {
+      const float ra = table[4 * q + 2], rb = table[4 * q + 3];
+#pragma unroll
+      for (int j = 0; j < EPL; ++j) {
+        adam0(p0[j], m0[j], v0[j], ra, rb, s);
+        if (BF) p0[j] = ncf_round_bf16(p0[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < EPL; ++j) {
+    stp<BF>(t.p0, o + j * LPR, p0[j]); t.m0[o + j * LPR] = m0[j]; t.v0[o + j * LPR] = v0[j];
+  }
+}
+
+// ---- both id kinds per launch (k = kind)
+struct PairArgs {
+  TablePtrs t[2];
+  const int64_t* ids[2];
+  int32_t* stamp[2];
+  int64_t rows[2];
+  int bf;            // parameter rows are bf16 (host-side dispatch only)
+};
+
+inline PairArgs pair_args(const ncf_table_pair* p, int n) {
+  PairArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int k = 0; k < n && k < 2; ++k) {
+    a.t[k] = TablePtrs{p[k].p0, p[k].m0, p[k].v0, p[k].p1, p[k].m1, p[k].v1, p[k].g0, p[k].g1};
+    a.ids[k] = p[k].row_ids;
+    a.stamp[k] = p[k].stamp;
+    a.rows[k] = p[k].rows;
+  }
+  a.bf = p[0].param_dtype == NCF_DTYPE_BF16;
+  return a;
+}
+
+// Block bx (of ncf_cdiv(max_n * Replay<D>::LPR, 256), 256 threads) of the catch-up of kind k's
+// listed rows ids[k][0 .. count[k]) to clock->t + target_rel.
+template <int D, bool BF>
+__device__ __forceinline__ void pairs_catchup_body(const PairArgs& a, int k, uint32_t bx,
+                                                   const uint32_t* __restrict__ count,
+                                                   int64_t max_n, int32_t target_rel,
+                                                   const ncf_step_clock* __restrict__ clock,
+                                                   const float* __restrict__ table,
+                                                   const AdamScalars& s, int lock) {
+  constexpr int L = Replay<D>::LPR;   // lanes per row
+  const int64_t tt = (int64_t)bx * 256 + threadIdx.x;
+  const int64_t c = tt / L;
+  const int sub = (int)(tt % L);
+  if (c >= max_n || c >= (int64_t)count[k]) return;
+  const int32_t target = clock->t + target_rel;
+  const int64_t row = a.ids[k][c];
+  int32_t* stamp = a.stamp[k];
+  const int32_t from = stamp[row];
+  catch_up_row<D, BF>(a.t[k], row, sub, from, target, table, s);
+  // lock: every listed row is marked in flight (current through target, its gradient step still
+  // to come: the step's apply writes the plain stamp back); replays of other rows skip it
+  if (sub == 0 && (lock || from < target)) stamp[row] = lock ? (target | NCF_STAMP_LOCK) : target;
+}
+
+}  // namespace
+}  // namespace ncf_adam
+
+#define NCF_DISPATCH_DIM(D, FN, ...)                                          \
+  switch (D) {                                                                \
+    case 16: return FN<16>(__VA_ARGS__);                                      \
+    case 32: return FN<32>(__VA_ARGS__);                                      \
+    case 64: return FN<64>(__VA_ARGS__);                                      \
+    case 128: return FN<128>(__VA_ARGS__);                                    \
+    case 256: return FN<256>(__VA_ARGS__);                                    \
+    default: ncf_set_error("unsupported dim %lld", (long long)D); return NCF_ERR_ARG; \
+  }

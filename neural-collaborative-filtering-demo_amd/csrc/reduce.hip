@@ -12,121 +12,97 @@
 // The summation order of every output depends only on (P, chunking) — never on scheduling —
 // and is the order of ncf_reduce_parts (ncf_common.h), so a deferred reduction is bit-identical
 // to the inline one.
+//
+// ncf_reduce_batch_catchup is the same two stages with the deferred table Adam's late catch-up
+// of the next batch's rows (adam_catchup_dev.h) inside the first stage-1 launch
+// (k_reduce1_catchup): the memory-bound reduce blocks and the latency-bound replay chains share
+// the CUs on the step's own queue, with no cross-queue event between them.
 #include "ncf_common.h"
+#include "reduce_dev.h"          // stage 1 and the launch arguments (shared with the fused launch)
+#include "adam_catchup_dev.h"
+
+using namespace ncf_reduce;
+using namespace ncf_adam;
 
 namespace {
 
-constexpr int kPB = 64;          // partials per stage-1 chunk
-constexpr int kMaxPerLaunch = 24; // descriptors per launch (kernel-argument size)
 // ncf_reduce_set_vec: 0 one column per lane, 1 four columns per lane (16-byte loads, 16 in
 // flight per thread; the default)
 int VEC_LANES = 1;
+// ncf_reduce_catchup_set_order: which class of blocks of k_reduce1_catchup takes the low block
+// indices and so dispatches first (0: the reduce blocks, the default; 1: the catch-up's replay
+// chains; 2: the two interleaved).  Measured: DESIGN §15.
+int TAIL_ORDER = 0;
 
-struct BatchArgs {
-  ncf_reduce_desc d[kMaxPerLaunch];
-  int64_t scr[kMaxPerLaunch];        // scratch offset (floats) of multi-chunk descriptors
-  uint32_t first[kMaxPerLaunch + 1]; // first block of descriptor i (prefix over blocks)
-  int32_t chunks[kMaxPerLaunch];
-  int32_t vec[kMaxPerLaunch];        // 16-byte (four-column) lanes
-  int32_t count;
-};
-
-__device__ __forceinline__ int find_desc(const BatchArgs& a, uint32_t b) {
-  int i = 0;
-  while (i + 1 < a.count && a.first[i + 1] <= b) ++i;
-  return i;
-}
-
-__device__ __forceinline__ void store_out(const ncf_reduce_desc& d, int64_t i, float t) {
-  float* o = d.out + (i / d.cols) * d.ldo + (i % d.cols);
-  const float v = d.scale * t;
-  *o = d.accumulate ? *o + v : v;
-}
-
-template <typename T> __device__ __forceinline__ T zero();
-template <> __device__ __forceinline__ float zero<float>() { return 0.0f; }
-template <> __device__ __forceinline__ float4 zero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-// Stage-1 sum of wave w's partials (rows pb + w, pb + w + 4, ... < pe) at element(s) i: T = float
-// (one column per lane) or float4 (four adjacent columns per lane, 16-byte loads: each column's
-// additions are the scalar form's, in the same order — the same bits).
-template <typename T>
-__device__ __forceinline__ T stage1_sum(const float* __restrict__ part, int64_t stride, int64_t i,
-                                        int pb, int pe, int w) {
-  T a0 = zero<T>(), a1 = zero<T>(), a2 = zero<T>(), a3 = zero<T>();
-  int p = pb + w;
-  // 16 loads in flight per thread (a full 64-partial chunk in one batch), summed in the order
-  // of the loop below (accumulator j % 4 takes partial p + 4j): the same bits, without the
-  // four dependent rounds of HBM latency
-  for (; p + 60 < pe; p += 64) {
-    T v[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = *(const T*)(part + (int64_t)(p + 4 * j) * stride + i);
-#pragma unroll
-    for (int j = 0; j < 16; j += 4) {
-      a0 += v[j];
-      a1 += v[j + 1];
-      a2 += v[j + 2];
-      a3 += v[j + 3];
-    }
-  }
-  for (; p + 12 < pe; p += 16) {
-    a0 += *(const T*)(part + (int64_t)p * stride + i);
-    a1 += *(const T*)(part + (int64_t)(p + 4) * stride + i);
-    a2 += *(const T*)(part + (int64_t)(p + 8) * stride + i);
-    a3 += *(const T*)(part + (int64_t)(p + 12) * stride + i);
-  }
-  for (; p < pe; p += 4) a0 += *(const T*)(part + (int64_t)p * stride + i);
-  return (a0 + a1) + (a2 + a3);
-}
-
-// One 256-thread block per (descriptor, 64 lanes of columns, chunk of <= 64 partials); a
-// descriptor flagged vec (a.vec: L, stride and the partial base 16-byte multiples) takes four
-// columns per lane — 256 per block, 16-byte loads (stage 1 streams the batch's ~76 MB of
-// weight-gradient partial sets at C2: the wide loads carry it nearer the HBM rate).
 __global__ __launch_bounds__(256) void k_reduce_batch1(const BatchArgs a, float* __restrict__ scratch) {
   __shared__ float4 red[4][64];
-  const int di = find_desc(a, blockIdx.x);
-  const ncf_reduce_desc& d = a.d[di];
-  const int ch = a.chunks[di];
-  const bool vec = a.vec[di] != 0;
-  const int vw = vec ? 4 : 1;
-  const uint32_t local = blockIdx.x - a.first[di];
-  const uint32_t gx = (uint32_t)((d.L + 64 * vw - 1) / (64 * vw));
-  const int64_t i = ((int64_t)(local % gx) * 64 + (threadIdx.x & 63)) * vw;
-  const int y = (int)(local / gx);
-  const int w = threadIdx.x >> 6;
-  const int l = threadIdx.x & 63;
-  const int pb = ch > 1 ? y * kPB : 0;
-  const int pe = ch > 1 ? min(d.P, pb + kPB) : d.P;
-  if (vec) {
-    float4 s = zero<float4>();
-    if (i < d.L) s = stage1_sum<float4>(d.part, d.stride, i, pb, pe, w);
-    red[w][l] = s;
-    __syncthreads();
-    if (w == 0 && i < d.L) {
-      const float4 t = (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
-      if (ch > 1) {
-        *(float4*)(scratch + a.scr[di] + (int64_t)y * d.L + i) = t;
-      } else {
-        store_out(d, i, t.x);
-        store_out(d, i + 1, t.y);
-        store_out(d, i + 2, t.z);
-        store_out(d, i + 3, t.w);
-      }
-    }
-    return;
-  }
-  float s = 0.0f;
-  if (i < d.L) s = stage1_sum<float>(d.part, d.stride, i, pb, pe, w);
-  red[w][l].x = s;
-  __syncthreads();
-  if (w == 0 && i < d.L) {
-    const float t = (red[0][l].x + red[1][l].x) + (red[2][l].x + red[3][l].x);
-    if (ch > 1) scratch[a.scr[di] + (int64_t)y * d.L + i] = t;
-    else store_out(d, i, t);
-  }
+  reduce1_body(a, scratch, blockIdx.x, red);
 }
+
+// Stage 1 of one launch group and the catch-up of both id kinds' listed rows (lock = 0) in one
+// 1-D grid: nred reduce blocks (reduce1_body, as k_reduce_batch1) and npairs * ncx catch-up
+// blocks (pairs_catchup_body, as k_pairs_catchup's grid (ncx, npairs)).  The two classes touch
+// disjoint memory (gradient partials and outputs; table rows, moments and stamps).
+// The replay is VALU-bound and wants every wave slot: the kernel is held to 64 registers (8
+// waves per SIMD, 8 blocks per CU), which the reduce blocks meet with kTailLoads = 4 loads in
+// flight per thread where k_reduce_batch1 keeps 16 (90 registers, 5 waves) — the same additions
+// in the same order.  At 90 registers the fused launch took 33 us of the C2 step, at 64 with 8
+// loads (28 B of scratch per lane) 28 us, with 4 loads (50 registers at D <= 128, no scratch)
+// 27 us; DESIGN §15.
+constexpr int kTailLoads = 4;
+template <int D, bool BF>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_reduce1_catchup(const BatchArgs a,
+                                                         float* __restrict__ scratch, uint32_t nred,
+                                                         const PairArgs pa,
+                                                         const uint32_t* __restrict__ count,
+                                                         int64_t max_n, int32_t target_rel,
+                                                         const ncf_step_clock* __restrict__ clock,
+                                                         const float* __restrict__ table,
+                                                         const AdamScalars s, uint32_t ncx,
+                                                         int order) {
+  __shared__ float4 red[4][64];
+  const uint32_t ncatch = gridDim.x - nred;
+  uint32_t b = blockIdx.x;
+  bool catchup;
+  int k = 0;
+  if (order == 2) {
+    // interleaved: groups of one catch-up block per kind and one reduce block while both
+    // classes last (the listed rows sit in each kind's low blocks), then the longer class
+    const uint32_t np = ncatch / ncx, per = np + 1;
+    const uint32_t m = min(ncx, nred);
+    if (b < m * per) {
+      const uint32_t j = b % per;
+      catchup = j < np;
+      k = (int)j;
+      b /= per;
+    } else {
+      const uint32_t r = b - m * per;
+      catchup = ncx > nred;
+      k = catchup ? (int)(r % np) : 0;
+      b = m + (catchup ? r / np : r);
+    }
+  } else {
+    if (order == 1) {
+      catchup = b < ncatch;
+      if (!catchup) b -= ncatch;
+    } else {
+      catchup = b >= nred;
+      if (catchup) b -= nred;
+    }
+    if (catchup) {
+      k = (int)(b / ncx);
+      b %= ncx;
+    }
+  }
+  if (catchup)
+    pairs_catchup_body<D, BF>(pa, k, b, count, max_n, target_rel, clock, table, s, 0);
+  else
+    reduce1_body<kTailLoads>(a, scratch, b, red);
+}
+// the arguments travel by value in the kernel-argument segment (4 KB)
+static_assert(sizeof(BatchArgs) + sizeof(PairArgs) + sizeof(AdamScalars) + 96 <= 4096,
+              "k_reduce1_catchup: kernel arguments exceed 4 KB");
+
 
 // stage 2: one thread per output element (four per thread for a vec descriptor) of the
 // multi-chunk descriptors
@@ -218,16 +194,49 @@ extern "C" int64_t ncf_reduce_batch_scratch(const ncf_reduce_list* list) {
   return f;
 }
 
-extern "C" int ncf_reduce_batch(const ncf_reduce_list* list, float* scratch,
-                                int64_t scratch_floats, void* stream) {
-  NCF_CHECK_ARG(list && list->count >= 0 && list->count <= NCF_REDUCE_LIST_MAX,
-                "ncf_reduce_batch: bad list");
+
+namespace {
+
+// the catch-up that rides in the first stage-1 launch (ncf_reduce_batch_catchup)
+struct Tail {
+  PairArgs pa;
+  int npairs;
+  int64_t dim;
+  const uint32_t* count;
+  int64_t max_n;
+  int32_t target_rel;
+  const ncf_step_clock* clock;
+  const float* table;
+  AdamScalars s;
+};
+
+template <int D>
+int fused_d(const BatchArgs& a1, float* scratch, uint32_t b1, const Tail& t, hipStream_t st) {
+  const uint32_t ncx = (uint32_t)ncf_cdiv(t.max_n * Replay<D>::LPR, 256);
+  const dim3 grid(b1 + (uint32_t)t.npairs * ncx);
+  if (t.pa.bf)
+    hipLaunchKernelGGL((k_reduce1_catchup<D, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
+  else
+    hipLaunchKernelGGL((k_reduce1_catchup<D, false>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
+  NCF_CHECK_LAUNCH("ncf_reduce_batch_catchup(stage 1 + catch-up)");
+  return NCF_OK;
+}
+
+int fused_launch(const BatchArgs& a1, float* scratch, uint32_t b1, const Tail& t, hipStream_t st) {
+  NCF_DISPATCH_DIM(t.dim, fused_d, a1, scratch, b1, t, st);
+}
+
+// Every listed reduction, a launch group of <= kMaxPerLaunch descriptors at a time.  With
+// `tail` (max_n > 0, a non-empty list) the first group's stage 1 is the fused launch.
+int run_list(const char* who, const ncf_reduce_list* list, float* scratch, int64_t scratch_floats,
+             const Tail* tail, hipStream_t st) {
+  NCF_CHECK_ARG(list && list->count >= 0 && list->count <= NCF_REDUCE_LIST_MAX, "%s: bad list",
+                who);
   if (scratch_floats < ncf_reduce_batch_scratch(list)) {
-    ncf_set_error("ncf_reduce_batch: scratch %lld < %lld floats", (long long)scratch_floats,
+    ncf_set_error("%s: scratch %lld < %lld floats", who, (long long)scratch_floats,
                   (long long)ncf_reduce_batch_scratch(list));
     return NCF_ERR_WORKSPACE;
   }
-  hipStream_t st = (hipStream_t)stream;
   int64_t scr_off = 0;
   for (int base = 0; base < list->count; base += kMaxPerLaunch) {
     BatchArgs a1, a2;
@@ -237,7 +246,7 @@ extern "C" int ncf_reduce_batch(const ncf_reduce_list* list, float* scratch,
     for (int j = 0; j < kMaxPerLaunch && base + j < list->count; ++j) {
       const ncf_reduce_desc& d = list->d[base + j];
       NCF_CHECK_ARG(d.part && d.out && d.L >= 0 && d.P >= 1 && d.cols >= 1 && d.stride >= d.L,
-                    "ncf_reduce_batch: bad descriptor %d", base + j);
+                    "%s: bad descriptor %d", who, base + j);
       const int c = chunks_of(d.P);
       const bool vec = VEC_LANES > 0 && d.L % 4 == 0 && d.stride % 4 == 0 &&
                        ((uintptr_t)d.part & 15) == 0 &&
@@ -264,7 +273,10 @@ extern "C" int ncf_reduce_batch(const ncf_reduce_list* list, float* scratch,
     }
     a1.first[a1.count] = b1;
     a2.first[a2.count] = b2;
-    if (b1 > 0) {
+    if (tail && base == 0) {
+      const int rc = fused_launch(a1, scratch, b1, *tail, st);
+      if (rc != NCF_OK) return rc;
+    } else if (b1 > 0) {
       hipLaunchKernelGGL(k_reduce_batch1, dim3(b1), dim3(256), 0, st, a1, scratch);
       NCF_CHECK_LAUNCH("ncf_reduce_batch(stage 1)");
     }
@@ -274,4 +286,44 @@ extern "C" int ncf_reduce_batch(const ncf_reduce_list* list, float* scratch,
     }
   }
   return NCF_OK;
+}
+
+}  // namespace
+
+extern "C" int ncf_reduce_batch(const ncf_reduce_list* list, float* scratch,
+                                int64_t scratch_floats, void* stream) {
+  return run_list("ncf_reduce_batch", list, scratch, scratch_floats, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int64_t ncf_reduce_catchup_set_order(int64_t order) {
+  const int was = TAIL_ORDER;
+  if (order >= 0) TAIL_ORDER = order > 2 ? 2 : (int)order;
+  return was;
+}
+
+// ncf_reduce_batch(list, ...) and ncf_adam_pairs_catchup_lock_clock(pairs, ..., lock = 0, ...) on
+// one stream, with the catch-up inside the first group's stage-1 launch: the same bits as the
+// two calls (the same device bodies; the two touch disjoint memory).
+extern "C" int ncf_reduce_batch_catchup(const ncf_reduce_list* list, float* scratch,
+                                        int64_t scratch_floats, const ncf_table_pair* pairs,
+                                        int npairs, int64_t dim, const uint32_t* count,
+                                        int64_t max_n, int32_t target_rel,
+                                        const ncf_step_clock* clock, const float* step_table,
+                                        double beta1, double beta2, double eps,
+                                        double weight_decay, void* stream) {
+  NCF_CHECK_ARG(list && list->count >= 0 && list->count <= NCF_REDUCE_LIST_MAX,
+                "ncf_reduce_batch_catchup: bad list");
+  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table,
+                "ncf_reduce_batch_catchup: bad args");
+  if (max_n <= 0)
+    return run_list("ncf_reduce_batch_catchup", list, scratch, scratch_floats, nullptr,
+                    (hipStream_t)stream);
+  if (list->count == 0)
+    return ncf_adam_pairs_catchup_lock_clock(pairs, npairs, dim, count, max_n, target_rel, 0,
+                                             clock, step_table, beta1, beta2, eps, weight_decay,
+                                             stream);
+  const Tail tail{pair_args(pairs, npairs), npairs, dim, count, max_n, target_rel, clock,
+                  step_table, consts_of(beta1, beta2, eps, weight_decay)};
+  return run_list("ncf_reduce_batch_catchup", list, scratch, scratch_floats, &tail,
+                  (hipStream_t)stream);
 }

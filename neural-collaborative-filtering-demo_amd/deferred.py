@@ -63,6 +63,10 @@ def early_on(n: int) -> bool:
 # sweep and the sort, beside the dense-gradient reductions (memory-bound, like it) instead of
 # beside the compute-bound backward; nothing to lock (the step's rows already carry its stamp).
 # The next step then skips its own catch-up launch for that batch.
+# With trainer.FUSED_TAIL (the default) it does not go to the side stream at all: the step's own
+# stream waits once for the side stream (sweep and sort), and the catch-up runs inside the first
+# launch of the step's final reductions (ncf_reduce_batch_catchup; late_catchup_args) — still
+# beside them, without the event hop to the side stream and the one back.
 LATE_CATCHUP = True
 # HIP stream priority of the overlapped sweep's side stream (torch.cuda.Stream priority: 0 the
 # default, -1 high)
@@ -512,8 +516,26 @@ class DeferredTableAdam:
         rows["late_t"] = self.t + 1
         return True
 
+    def late_catchup_args(self, rows, n):
+        """The late catch-up of late_catchup() as the catch-up arguments of
+        ncf_reduce_batch_catchup (trainer.FUSED_TAIL: inside the first launch of the step's
+        final reductions, on the step's own stream, once that stream has joined the side
+        stream's sweep and sort); late_catchup_mark(rows) once it is queued."""
+        self._ensure(self.t + 2)
+        return (ctypes.addressof(self._next_pairs(rows)), 2, self.engine.model.mlp_embedding_dim,
+                ptr(rows["num_unique"]), n, 1, ptr(self.clock), ptr(self._table)) + self._consts()
+
+    def late_catchup_mark(self, rows):
+        rows["late_t"] = self.t + 1
+
     def _catchup_next(self, rows, n, stream):
         self._ensure(self.t + 2)
+        _lib.call("ncf_adam_pairs_catchup_lock_clock", ctypes.addressof(self._next_pairs(rows)), 2,
+                  self.engine.model.mlp_embedding_dim, ptr(rows["num_unique"]), n, 1, 0,
+                  ptr(self.clock), ptr(self._table), *self._consts(), stream)
+
+    def _next_pairs(self, rows):
+        """ncf_table_pair[2] whose row lists are the dedup set ``rows`` (cached per set)."""
         cache = self.__dict__.setdefault("_early_pairs", {})
         key = (getattr(self, "_gen", 0), rows["uniq_u"].data_ptr(), rows["uniq_i"].data_ptr())
         pairs = cache.get(key)
@@ -523,9 +545,7 @@ class DeferredTableAdam:
             pairs = cache[key] = self._pairs()
             for k, ids in enumerate((rows["uniq_u"], rows["uniq_i"])):
                 pairs[k].row_ids = ptr(ids)
-        _lib.call("ncf_adam_pairs_catchup_lock_clock", ctypes.addressof(pairs), 2,
-                  self.engine.model.mlp_embedding_dim, ptr(rows["num_unique"]), n, 1, 0,
-                  ptr(self.clock), ptr(self._table), *self._consts(), stream)
+        return pairs
 
     def fused_apply_args(self, w):
         """The arguments of the apply fused into the embedding backward (engine.backward

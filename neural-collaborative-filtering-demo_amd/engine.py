@@ -128,7 +128,13 @@ class Workspace:
             return
         self.dumf, self.dimf = e(n, Dm), e(n, Dm)
         self.dxu, self.dxi = e(n, D), e(n, D)
-        self.dq, self.dk, self.dv, self.do, self.dy = (e(n, D) for _ in range(5))
+        self.dq, self.dk, self.dv, self.do = (e(n, D) for _ in range(4))
+        # dY, the gradient at the attention block's output.  Zeros, not empty: the fused tower +
+        # attention backward (ncf_attn_mlp_bwd) keeps dY in LDS and never writes this buffer, so
+        # on that path it would hold whatever the allocator's block held before (NaN bit patterns
+        # included: the forward's Q-stash tag is one); a caller that hands it to the stand-alone
+        # attention backward then reads defined values.  Once per workspace, not per step.
+        self.dy = torch.zeros(n, D, **f)
         self.dS = e(max(1, g.B * g.H * g.M * g.M))
         self.dlin = [e(n, h) for h in g.hidden]
         self.da = [e(n, h) for h in g.hidden]
@@ -202,19 +208,24 @@ class Workspace:
         off, size = self.site_off[name]
         return self.red_ws[off:off + size]
 
-    def run_reductions(self, st, scratch: str = "red_scratch"):
+    def run_reductions(self, st, scratch: str = "red_scratch", catchup=None):
         """All gradient reductions deferred by this backward so far, in two launches (``scratch``:
         the workspace attribute of the scratch buffer — the early reductions on a side stream
-        take a second one, so both batches can be in flight)."""
+        take a second one, so both batches can be in flight).  ``catchup``: the arguments of the
+        late catch-up of the next batch's rows (DeferredTableAdam.late_catchup_args), which then
+        runs inside the first launch (ncf_reduce_batch_catchup, trainer.FUSED_TAIL)."""
         lst = self.red_list
-        if lst.count == 0:
+        if lst.count == 0 and catchup is None:
             return
         need = _lib.query("ncf_reduce_batch_scratch", lst.address)
         buf = getattr(self, scratch, None)
         if buf is None or buf.numel() < need:
             buf = torch.empty(max(need, 1), dtype=torch.float32, device=self.red_ws.device)
             setattr(self, scratch, buf)
-        _lib.call("ncf_reduce_batch", lst.address, ptr(buf), buf.numel(), st)
+        if catchup is not None:
+            _lib.call("ncf_reduce_batch_catchup", lst.address, ptr(buf), buf.numel(), *catchup, st)
+        else:
+            _lib.call("ncf_reduce_batch", lst.address, ptr(buf), buf.numel(), st)
         lst.count = 0
 
 
@@ -224,6 +235,9 @@ class NCFEngine:
     def __init__(self, model):
         self.model = model
         self.fork_hook = None     # callable(at): side-stream work the caller forks at that point
+        # (dedup set, rows) of the next batch, left by the tables_done hook of a backward for
+        # its final reductions to catch up in their first launch (trainer.FUSED_TAIL)
+        self.tail_catchup = None
         self.ws: Dict[tuple, Workspace] = {}
         self.flat = None
         self.flat_grad = None
@@ -1055,7 +1069,17 @@ class NCFEngine:
             tables_done()
         self.join(dev, joins)
         self._sweep_fork("reduce")
-        w.run_reductions(st)
+        tail, self.tail_catchup = self.tail_catchup, None
+        if tail is not None:
+            # the late catch-up of the next batch's rows inside the reductions' first launch, on
+            # this stream: one wait for the side stream (its sweep, and the sort of those rows
+            # behind it) instead of a fork to it and a join back
+            d = self.deferred
+            d.sweep_join()
+            w.run_reductions(st, catchup=d.late_catchup_args(*tail))
+            d.late_catchup_mark(tail[0])
+        else:
+            w.run_reductions(st)
         self.pending = w
 
     def _embedding_bwd_split(self, w, uid, iid, tbp, d_rows, st):

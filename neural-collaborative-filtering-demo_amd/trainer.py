@@ -52,6 +52,12 @@ EARLY_REDUCE = False
 # (ncf_embedding_bwd_reduce_apply_clock: a row steps where its gradient rows complete; the same
 # bits as the separate apply)
 FUSE_APPLY = True
+# The late catch-up of the next batch's rows (deferred.LATE_CATCHUP) inside the first launch of
+# the step's final reductions, on the step's own stream (ncf_reduce_batch_catchup), instead of
+# on the side stream beside them: the same overlap, without the two cross-queue event hops
+# (apply -> side stream, side stream -> flat Adam close) that sat on the step's critical chain.
+# Same bits (tests/test_gpu_tail_fused.py).  Measurements: DESIGN §15.
+FUSED_TAIL = True
 # The rolling sweep's period (every row current at least every SWEEP_EVERY steps).  A longer
 # period halves the sweep's HBM traffic beside the forward; the replayed element-steps are the
 # same in total (moved from the sweep to the catch-up, which now runs beside the reductions:
@@ -237,9 +243,17 @@ class FusedTrainStep:
     def _tables_done(self):
         """Engine hook, right after the embedding backward with the table apply fused in was
         queued: the late catch-up of the next batch's rows, if this step's prefetch sorted them
-        (at the sweep fork, in the forward or the backward) and no early catch-up ran."""
+        (at the sweep fork, in the forward or the backward) and no early catch-up ran.  With
+        FUSED_TAIL the set is handed to the engine, whose final reductions carry the catch-up in
+        their first launch on the step's stream; else it goes to the side stream here."""
         late, self._late_next = self._late_next, None
-        if late is not None:
+        if late is None:
+            return
+        if FUSED_TAIL and not EARLY_REDUCE:
+            # (_late_next is only ever set by an eager clocked step whose prefetch sorted the
+            # next batch behind the sweep, with LATE_CATCHUP and FUSE_APPLY on)
+            self.model.engine.tail_catchup = late
+        else:
             self._late_catchup(*late)
 
     def _late_catchup(self, s, n):
