@@ -989,7 +989,8 @@ int ncf_adam_pairs_catchup_clock(const ncf_table_pair* pairs, int npairs, int64_
                                  void* stream);
 /* Stamps at or above NCF_STAMP_LOCK (0x40000000) compare above any target: the catch-up kernels
  * leave such rows alone.  ncf_adam_pairs_catchup_lock_clock with lock = 1 sets it on the listed
- * rows (caught up through the target, their gradient step of this step still to come; the
+ * rows it brought to the target or found there; a listed row already locked, or ahead of the
+ * target, keeps its stamp (caught up through the target, their gradient step of this step still to come; the
  * apply writes the plain stamp back); with lock = 0 and target_rel = 1 it is the early catch-up
  * of the NEXT batch's rows through the step now running, on a side stream beside its backward
  * (rows of this step's batch are locked and skipped).  The reference's Adam.step over every row

@@ -188,8 +188,11 @@ __device__ __forceinline__ void pairs_catchup_body(const PairArgs& a, int k, uin
   const int32_t from = stamp[row];
   catch_up_row<D, BF>(a.t[k], row, sub, from, target, table, s);
   // lock: every listed row is marked in flight (current through target, its gradient step still
-  // to come: the step's apply writes the plain stamp back); replays of other rows skip it
-  if (sub == 0 && (lock || from < target)) stamp[row] = lock ? (target | NCF_STAMP_LOCK) : target;
+  // to come: the step's apply writes the plain stamp back); replays of other rows skip it.  A
+  // listed row that is locked already, or ahead of the target, keeps its stamp: it was not
+  // brought to the target, and writing target | LOCK over s | LOCK would drop the steps it owes
+  if (sub == 0 && (from < target || (lock && from == target)))
+    stamp[row] = lock ? (target | NCF_STAMP_LOCK) : target;
 }
 
 }  // namespace

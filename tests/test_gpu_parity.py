@@ -735,12 +735,13 @@ def test_non_adam_optimizer_gets_dense_table_grads(f2):
 
 # ----------------------------------------------------------------------------- deferred Adam
 def _fused_run(deferred, steps, sweep_every=64, U=3000, I=500, B=64, seed=11, dropout=0.0,
-               lr_at=None, on_step=None, pipelined=False, **kw):
+               lr_at=None, on_step=None, pipelined=False, D=64, hidden=(256, 128, 64), H=4, **kw):
     """``pipelined``: every step is told the next batch (FusedTrainStep(next=...): the id sort
-    and the early catch-up of the next batch's rows run a step ahead on the side stream)."""
+    and the early catch-up of the next batch's rows run a step ahead on the side stream).
+    ``D``, ``hidden``, ``H``: the embedding width of both collections, the tower, the heads."""
     from ncf_amd.trainer import FusedTrainStep
     torch.manual_seed(seed)
-    m = ncf.AdvancedNCF(U, I, 5, 24, 64, 64, 32, [256, 128, 64], 4, dropout, 4).to(DEV)
+    m = ncf.AdvancedNCF(U, I, 5, 24, D, D, 32, list(hidden), H, dropout, 4).to(DEV)
     step = FusedTrainStep(m, lr=1e-3, weight_decay=1e-5, deferred=deferred, sweep_every=sweep_every,
                           **kw)
     g = torch.Generator().manual_seed(seed + 1)
@@ -1117,6 +1118,24 @@ def test_deferred_adam_bitwise_equals_dense(sweep_every, steps):
     only)."""
     a_sd, a_m = _fused_run(False, steps)
     b_sd, b_m = _fused_run(True, steps, sweep_every=sweep_every)
+    for k in a_sd:
+        assert torch.equal(a_sd[k], b_sd[k]), k
+    for k in a_m:
+        assert torch.equal(a_m[k][0], b_m[k][0]) and torch.equal(a_m[k][1], b_m[k][1]), k
+
+
+@pytest.mark.parametrize("D,H,hidden", [(16, 1, (64, 32)), (32, 2, (256, 128, 64)),
+                                        (128, 4, (256, 128, 64)), (256, 4, (256, 128, 64))])
+def test_deferred_adam_bitwise_equals_dense_other_widths(D, H, hidden):
+    """The deferred + clock schedule against the dense sweep, bit for bit, at the other widths
+    NCF_DISPATCH_DIM takes: 24 steps across three rounds of the rolling sweep (sweep_every = 8).
+    D < 64 shares a wave among 4 or 2 rows in the replay, D = 256 gives a lane 4 columns.
+    FusedTrainStep(deferred=True) refuses none of the four: trainer.py refuses only
+    mf_embedding_dim != mlp_embedding_dim, and engine.py sends a tower or an attention shape the
+    fused kernels do not take down the per-layer path (head dims 16, 16, 32, 64 here)."""
+    kw = dict(U=700, I=300, D=D, H=H, hidden=hidden)
+    a_sd, a_m = _fused_run(False, 24, **kw)
+    b_sd, b_m = _fused_run(True, 24, sweep_every=8, clock=True, **kw)
     for k in a_sd:
         assert torch.equal(a_sd[k], b_sd[k]), k
     for k in a_m:
