@@ -544,6 +544,31 @@ int ncf_temporal_bwd(const int64_t* hour, const int64_t* day, const int64_t* mon
                      const float* grad_out, int64_t dim, float* grad_hour, float* grad_day,
                      float* grad_month, void* stream);
 
+/* ---- backward of forward_simple(hour) (architecture.py:409-485), hour_bwd.hip --------------
+ * Item rows are scaled by s = 1 + scale_factor * item_scale (item_scale = the projected hour
+ * embedding, [n, dim]).  ncf_item_scale_bwd takes the gradients w.r.t. the scaled LN'd item rows
+ * (MF, MLP; [n, dim]) and, in place, makes them the gradients w.r.t. the unscaled rows (x s);
+ * grad_scale[n, dim] = scale_factor * (g_mf * y + g_mlp * z) with y, z the unscaled LN'd rows,
+ * recomputed from the table rows (never divided out of a scaled row: s may be 0).  dim 16 / 32 /
+ * 64 / 128, fp32 tables; out-of-range ids read row 0 and raise err_flag as the gather does.
+ * ncf_hour_grad: grad_hour[24, dim] = per-hour sums of dte[n, dim] (leading dimension ld) plus,
+ * when add != NULL, add[n, dim] (leading dimension ld_add); deterministic two-stage ordered
+ * reduction in chunks of ncf_hour_grad_chunk() batch rows, no atomics, all 24 rows written.
+ * workspace: ncf_hour_grad_workspace(n, dim) floats.  dim 1..256.                             */
+int ncf_hour_rows(const int64_t* hour, int64_t n, const float* hour_embed, int64_t dim, float* out,
+                  int* err_flag, void* stream);   /* out[n, dim] = hour_embed[hour], any dim <= 256 */
+int64_t ncf_hour_grad_chunk(void);
+int64_t ncf_hour_grad_workspace(int64_t n, int64_t dim);
+int ncf_item_scale_bwd(const int64_t* item_ids, int64_t n, const float* mf_item,
+                       const float* mlp_item, int64_t num_items, int64_t dim,
+                       const float* mf_gamma, const float* mf_beta, const float* mlp_gamma,
+                       const float* mlp_beta, float eps, const float* item_scale,
+                       float scale_factor, float* grad_mf_item_ln, float* grad_mlp_item_ln,
+                       float* grad_scale, int* err_flag, void* stream);
+int ncf_hour_grad(const int64_t* hour, int64_t n, const float* dte, int64_t ld, const float* add,
+                  int64_t ld_add, int64_t dim, float* grad_hour, float* workspace,
+                  int64_t workspace_floats, void* stream);
+
 /* ---- a7: MLP tower row ops (ReLU -> LayerNorm -> Dropout), architecture.py:233-239 --------
  * Backward also returns grad_bias = column sums of grad_lin (the bias gradient of the Linear
  * that feeds the ReLU; nullable).                                                            */

@@ -211,6 +211,11 @@ SIGNATURES = {
     "ncf_nn_scan": (I32, [P, I64, I32, P, I64, I64, P, P, P, I64, I64, I32, P, P, P]),
     "ncf_temporal_fwd": (I32, [P, P, P, P, I64, P, P, P, P, I64, I64, P, P, P]),
     "ncf_temporal_bwd": (I32, [P, P, P, I64, P, I64, P, P, P, P]),
+    "ncf_hour_rows": (I32, [P, I64, P, I64, P, P, P]),
+    "ncf_hour_grad_chunk": (I64, []),
+    "ncf_hour_grad_workspace": (I64, [I64, I64]),
+    "ncf_item_scale_bwd": (I32, [P, I64, P, P, I64, I64, P, P, P, P, F32, P, F32, P, P, P, P, P]),
+    "ncf_hour_grad": (I32, [P, I64, P, I64, P, I64, I64, P, P, I64, P]),
 }
 
 

@@ -29,7 +29,9 @@ class MultiHeadAttention(nn.Module):
     query of length L_q and key/value of length L_k, each 1..64 and equal or not, a 2-D [B, D]
     input counting as length 1 (``sequence_attention(user_row, history, history)`` returns
     [B, 1, D]), head dim 8 / 16 / 32 / 64 and the reference's optional mask; CategoryHierarchy
-    (L = 1) goes through ``attend_single_key``."""
+    (L = 1) goes through ``attend_single_key``.  As ``user_product_attention`` of a
+    ``forward_simple(hour)`` training step (``model.hour_backward``) it attends over one key:
+    v_proj and out_proj train, q_proj and k_proj receive zero gradients."""
 
     def __init__(self, embed_dim: int, num_heads: int = 4, dropout: float = 0.1):
         super().__init__()
@@ -109,6 +111,7 @@ class _NCFTrainFunction(torch.autograd.Function):
         if w is None:
             w = engine.forward(uid, iid, M, True, drop_p, seed,
                                prepare=d.prepare if d is not None else None)
+        w.no_tape = False
         ctx.engine, ctx.w, ctx.drop_p, ctx.seed = engine, w, drop_p, seed
         ctx.save_for_backward(uid, iid)
         return w.prob.view(-1, 1).clone()
@@ -129,6 +132,66 @@ class _NCFTrainFunction(torch.autograd.Function):
                 p.grad = v
         for p, g in prev:  # gradient accumulation across backward() calls
             p.grad.add_(g)
+        eng.grad_version = eng.flat_grad._version
+        return (None,) * 7
+
+
+class _NCFHourTrainFunction(torch.autograd.Function):
+    """Forward + backward of forward_simple(user_ids, product_ids, hour) in training mode
+    (``model.hour_backward = True``): _NCFTrainFunction's sibling, with the same
+    pending / grad-anchor behaviour.  ``hour`` = {"tp" [n, D], "te" [n, T], "hour" [n], "f",
+    "w_p" (the projection's weight, None when T == D), "proj" (an nn.Linear that takes a
+    gradient, or None)}.  Dense gradients land in the flat buffer (mlp.0.weight's temporal columns
+    included), the tables' stay compact, and temporal_encoding.hour_embed.weight gets a dense
+    [24, T] .grad of its own (it is no part of the flat buffer: torch's Adam steps it).  An hour
+    step never records or replays a launch tape, and it breaks the recording streak."""
+
+    @staticmethod
+    def forward(ctx, engine, uid, iid, drop_p, seed, hour, anchor):
+        d = engine.deferred
+        _settle_pending(engine, uid.device)
+        if engine.tapes is not None:
+            engine.tapes.streak = (None, 0)
+        w = engine.forward(uid, iid, 1, True, drop_p, seed,
+                           prepare=d.prepare if d is not None else None,
+                           temporal=(hour["tp"], hour["f"], hour["te"]))
+        w.no_tape = True          # (StepTapes.step: this step's optimizer phase stays eager)
+        ctx.engine, ctx.w, ctx.drop_p, ctx.seed, ctx.hour = engine, w, drop_p, seed, hour
+        ctx.save_for_backward(uid, iid)
+        return w.prob.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .ops import _wgrad
+        uid, iid = ctx.saved_tensors
+        eng, w, hour = ctx.engine, ctx.w, ctx.hour
+        views = eng.grad_views()
+        prev = [(p, p.grad.clone()) for p, _ in views if p.grad is not None and p.requires_grad]
+        _settle_pending(eng, grad_out.device)
+        gp = grad_out.reshape(-1).to(torch.float32).contiguous()
+        eng.backward(w, uid, iid, gp, None, ctx.drop_p, ctx.seed, temporal=hour)
+        for p, v in views:
+            if p.requires_grad:
+                p.grad = v
+        for p, g in prev:  # gradient accumulation across backward() calls
+            p.grad.add_(g)
+        hb = w.hour(hour["te"].shape[1])
+        hw = eng.model.temporal_encoding.hour_embed.weight
+        if hw.requires_grad:
+            if hw.grad is None:
+                hw.grad = hb["dhour"].clone()
+            else:
+                hw.grad.add_(hb["dhour"])
+        lin = hour.get("proj")
+        if lin is not None:        # dW_p = dtpᵀ · te, db_p = Σ dtp
+            n, D = w.g.n, w.g.D
+            gw = torch.empty_like(hour["w_p"])
+            gb = torch.empty(D, device=gw.device)
+            _wgrad(hb["dtp"], hour["te"], gw, n, D, hb["T"], gb)
+            for p, g in ((lin.weight, gw), (lin.bias, gb)):
+                if p is not None and p.requires_grad:
+                    g = g.to(device=p.device, dtype=p.dtype).view_as(p)
+                    p.grad = g if p.grad is None else p.grad.add_(g)
         eng.grad_version = eng.flat_grad._version
         return (None,) * 7
 
@@ -286,14 +349,29 @@ class AdvancedNCF(nn.Module):
 
     def forward_simple(self, user_ids, product_ids, hour=None):
         """(:409-485) With hour=None this is the eval forward with M=1 per pair; with hour the
-        reference's temporal variant, including its fresh random projection per call."""
+        reference's temporal variant, including its fresh random projection per call.
+
+        In training mode with gradients enabled the hour variant is refused unless
+        ``model.hour_backward = True`` (a plain attribute like ``validate_ids``: no parameter, no
+        buffer, no state_dict key).  With the switch the call returns a [n] tensor attached to
+        autograd: ``loss.backward()`` gives the four tables their compact pending gradients and
+        every dense parameter its view of the flat gradient buffer, as ``forward()`` does — with
+        ``mlp.0.weight.grad``'s temporal columns non-zero and q_proj / k_proj gradients zero
+        tensors (softmax over one key is constant) — and ``temporal_encoding.hour_embed.weight``
+        a dense [24, T] ``.grad`` (rows of absent hours exactly 0).  When temporal_dim !=
+        mf_embedding_dim each call draws a fresh nn.Linear(T, D), as the reference does, and
+        treats it as a constant: pin it with ``ops.forward_simple_hour(projection=...)``
+        (DESIGN §17)."""
         if hour is not None:
             from .ops import forward_simple_hour
             if (self.training and torch.is_grad_enabled()
+                    and not getattr(self, "hour_backward", False)
                     and any(p.requires_grad for p in self.parameters())):
                 # (its forward runs in training mode, dropout included, under torch.no_grad())
                 raise NotImplementedError("forward_simple(hour=...) has no backward on the "
-                                          "accelerated path; call it under torch.no_grad()")
+                                          "accelerated path by default; call it under "
+                                          "torch.no_grad(), or set model.hour_backward = True "
+                                          "to train through it")
             return forward_simple_hour(self, user_ids, product_ids, hour)
         eng = self._engine
         if self.training and torch.is_grad_enabled():

@@ -19,29 +19,9 @@
 // same bits (tests/test_gpu_parity.py::test_gather_two_float4_lanes_bitwise_equals_one_float4).
 #pragma clang fp contract(off)
 
+#include "row_ln_dev.h"   // RowLN<D>, safe_id (shared with hour_bwd.hip)
+
 namespace {
-
-template <int D>
-struct RowLN {
-  static constexpr int L = D / 4;
-  __device__ __forceinline__ static float4 ln(float4 x, float4 g, float4 b, float eps) {
-    float s = group_sum<L>(x.x + x.y + x.z + x.w);
-    float mean = s * (1.0f / D);
-    float4 c = make_float4(x.x - mean, x.y - mean, x.z - mean, x.w - mean);
-    float q = group_sum<L>(c.x * c.x + c.y * c.y + c.z * c.z + c.w * c.w);
-    float rstd = 1.0f / sqrtf(q * (1.0f / D) + eps);
-    return make_float4(c.x * rstd * g.x + b.x, c.y * rstd * g.y + b.y, c.z * rstd * g.z + b.z,
-                       c.w * rstd * g.w + b.w);
-  }
-};
-
-__device__ __forceinline__ int64_t safe_id(int64_t id, int64_t rows, int* err, bool report) {
-  if (id < 0 || id >= rows) {
-    if (err && report) atomicOr(err, 1);
-    return 0;
-  }
-  return id;
-}
 
 template <int D, bool BF = false>
 __global__ __launch_bounds__(256) void k_gather_ln_gmf(

@@ -176,6 +176,23 @@ class Workspace:
         self.uniq_i = torch.empty(max(1, n), dtype=torch.int64, device=device)
         self.num_unique = torch.zeros(2, dtype=torch.int32, device=device)
 
+    def hour(self, T: int) -> dict:
+        """Buffers of forward_simple(hour) (allocated once per workspace and temporal width):
+        ``yt`` = the tower's input [attention ‖ hour_E[h]]; for the training step also ``dyt``
+        (its gradient, layer 0's dX at K = D + T), ``dtp`` (the scale's gradient), ``dhour``
+        (hour_embed's [24, T] gradient of the last backward) and the partials of its reduction."""
+        h = getattr(self, "_hour", None)
+        if h is None or h["T"] != T:
+            g = self.g
+            dev = self.prob.device
+            e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+            h = {"T": T, "yt": e(g.n, g.D + T)}
+            if self.train:
+                h.update(dyt=e(g.n, g.D + T), dtp=e(g.n, g.D), dhour=e(24, T),
+                         parts=e(max(1, _lib.query("ncf_hour_grad_workspace", g.n, T))))
+            self._hour = h
+        return h
+
     @staticmethod
     def splits_for(m_out: int, k_out: int, rows: int) -> int:
         """Row slabs of a weight-gradient product: ~160 batch rows per wave (a few waves per SIMD
@@ -470,8 +487,10 @@ class NCFEngine:
         holding prob (and, when ``train``, everything the backward needs).  ``prepare(w, uid,
         iid, stream)`` runs before the gathers (the deferred Adam dedups the ids there and
         brings exactly those rows current).  ``temporal = (item_scale [n,D], factor, te [n,T])``
-        is forward_simple's hour path (eval, M = 1): item rows scaled in the gather and the MLP
-        fed [attention ‖ te] instead of [attention ‖ 0].  ``table_ld``: the ``tables`` rows are
+        is forward_simple's hour path (M = 1): item rows scaled in the gather and the MLP
+        fed [attention ‖ te] instead of [attention ‖ 0]; with ``train`` it stashes what
+        ``backward(temporal=...)`` needs (per-layer launches, the tower's input in
+        ``w.hour(T)["yt"]``).  ``table_ld``: the ``tables`` rows are
         that many floats apart (the row-sharded step's received rows read in place)."""
         dev = self._check_device()
         self.ensure_layout()
@@ -508,8 +527,8 @@ class NCFEngine:
             self._sweep_fork("gather")     # (a fork point after prepare, before the gather)
         else:
             self.sync_tables()
-        if temporal is not None and (train or M != 1):
-            raise ValueError("the temporal (hour) path is forward_simple's: eval, one item per group")
+        if temporal is not None and M != 1:
+            raise ValueError("the temporal (hour) path is forward_simple's: one item per group")
         # a2-a4: 4 gathers + mf_norm/mlp_norm + GMF  (architecture.py:286-287, 305-312)
         t_scale, t_factor = (temporal[0], temporal[1]) if temporal is not None else (None, 0.0)
         G = M if (GROUP_ROWS and ATTN_SHARE_Q and train and M > 1 and temporal is None
@@ -741,8 +760,10 @@ class NCFEngine:
         n = w.g.n
         D, H = w.g.D, w.g.H
         att = m.user_product_attention
-        if M == 1 and not train:
+        if M == 1 and (not train or temporal is not None):
             # softmax over a single key is exactly 1 -> the core returns V unchanged
+            # (the hour training step takes this branch too, so its forward is the no-grad
+            # call's launch for launch; its backward is _attention_bwd_hour)
             self._gemm(w.xi, D, 0, att.v_proj.weight, D, 1, w.v, D, n, D, D, bias=att.v_proj.bias, st=st)
             src = w.v
             if temporal is not None and drop_p > 0:
@@ -772,7 +793,7 @@ class NCFEngine:
             # forward_simple(hour): MLP input [attn ‖ hour_E[h]] (architecture.py:467-468)
             te = temporal[2]
             Tt = te.shape[1]
-            yt = torch.empty(n, D + Tt, device=dev)
+            yt = w.hour(Tt)["yt"]
             self._gemm(src, D, 0, att.out_proj.weight, D, 1, yt, D + Tt, n, D, D,
                        bias=att.out_proj.bias, st=st)
             yt[:, D:].copy_(te)
@@ -855,7 +876,7 @@ class NCFEngine:
                  targets: Optional[torch.Tensor], drop_p: float, seed: int,
                  loss_denominator: float = 0.0, tables=None, rows=None, uniq=None,
                  bf16: bool = False, grad_rows=None, table_ld: Optional[int] = None,
-                 reduce_side=None, fused_apply=None, tables_done=None):
+                 reduce_side=None, fused_apply=None, tables_done=None, temporal=None):
         """Gradients of every used parameter.  Dense grads land in the flat grad buffer; table
         grads stay compact (self.pending) for the fused Adam step.  ``reduce_side`` (a stream
         whose queued work the step joins before its dense Adam): the tower and attention
@@ -867,7 +888,11 @@ class NCFEngine:
         schedule).  ``tables_done()`` is called right after the embedding backward is queued
         (before the dense-gradient reductions).  ``grad_rows = (buf, rows_u,
         rows_i)``: the table gradients of unique row c go to row rows_*[c] of buf ([mf | mlp]
-        halves, 2 D floats per row: the row-sharded step's send buffer) instead of w.G."""
+        halves, 2 D floats per row: the row-sharded step's send buffer) instead of w.G.
+        ``temporal`` = {"tp", "te", "hour", "f", "w_p"}: the backward of a forward run with
+        ``temporal=`` (forward_simple(hour), M = 1): per-layer launches with layer 0
+        at K = D + T, the single-key attention backward, the item scale's backward before the
+        embedding backward, and hour_embed's gradient into ``w.hour(T)["dhour"]``."""
         m = self.model
         g = w.g
         n, D, H, M, hid = g.n, g.D, g.H, g.M, g.hidden
@@ -882,7 +907,14 @@ class NCFEngine:
         # a12 + a8 backward (trainer.py:271; architecture.py:245-252)
         gp = None if grad_prob is None else grad_prob.reshape(-1).to(torch.float32).contiguous()
         tg = None if targets is None else targets.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
-        fused = self.mlp_fused(D, hid)
+        fused = temporal is None and self.mlp_fused(D, hid)
+        hb = None
+        if temporal is not None:
+            if M != 1 or w.split is not None or bf16 or grad_rows is not None:
+                raise ValueError("the temporal (hour) backward is forward_simple's: one item per "
+                                 "group, fp32 tables of one width")
+            hb = w.hour(temporal["te"].shape[1])
+            Tt = hb["T"]
         if not fused:
             _lib.call("ncf_head_bwd", ptr(w.prob), ptr(gp), ptr(tg), ptr(w.mf_pred), ptr(w.mlp_pred),
                       ptr(w.a[-1]), n, hid[-1], ptr(m.mlp_output.weight), ptr(m.final[0].weight),
@@ -952,6 +984,8 @@ class NCFEngine:
                           ptr(w.site(f"relu{l}")), w.site(f"relu{l}").numel(),
                           w.red_list.address, st)
             xin, kin = (w.y, D) if l == 0 else (w.a[l - 1], hid[l - 1])
+            if l == 0 and hb is not None:      # layer 0 on [attention ‖ te]: K = D + T throughout
+                xin, kin = hb["yt"], D + Tt
             ldw = lin.weight.shape[1]
             dW = gv(f"mlp.{4 * l}.weight")
             if not (fused and self.mlp_fused_wgrad()):
@@ -967,10 +1001,17 @@ class NCFEngine:
                     w.run_wgrads(_lib.stream_ptr(dev), slot=0)
             if not fused:
                 dx = w.dy if l == 0 else w.da[l - 1]
+                if l == 0 and hb is not None:
+                    dx = hb["dyt"]
                 self._gemm(w.dlin[l], h, 0, lin.weight, ldw, 0, dx, kin, n, kin, h, st=st)
         # a5 backward: out_proj, core, q/k/v projections
         if fused_ta:
             pass     # (in the fused launch above)
+        elif hb is not None:
+            self._sweep_fork("attn_bwd", w)
+            self._attention_bwd_hour(w, hb, drop_p, seed, joins, st)
+            self._hour_scale_bwd(w, hb, iid, temporal, st)
+            self._zero_cols_of = None    # (mlp.0.weight.grad[:, D:] is written: not zero any more)
         elif self.attn_block(D, H, M):
             self._sweep_fork("attn_bwd", w)
             # core + projections backward and the four Linear gradients in one launch
@@ -1143,6 +1184,65 @@ class NCFEngine:
         self._gemm(w.dv, D, 0, att.v_proj.weight, D, 0, w.dxi, D, n, D, D, accum=True, st=st)
         self.join(dev, side[1:])
         joins.append(side[0])
+
+    def _attention_bwd_hour(self, w, hb, drop_p, seed, joins, st):
+        """a5 backward of the hour step (architecture.py:458-463 over one key): the softmax is the
+        constant 1, so y = out_proj(keep ⊙ v_proj(x_i)) — the forward's launches read backwards.
+        q_proj and k_proj (weight and bias) and the user rows get exact zeros, as autograd gives
+        them in the reference.  dY is layer 0's dX, read in place at leading dimension D + T."""
+        m = self.model
+        g = w.g
+        n, D, H = g.n, g.D, g.H
+        dev = w.prob.device
+        gv = self.grad_view
+        att = m.user_product_attention
+        a_ = "user_product_attention."
+        dy, ldy = hb["dyt"], D + hb["T"]
+        # (w.v holds the kept / dropped V rows: the forward's dropout ran in place)
+        self._wgrad(w, dy, ldy, w.v, D, gv(a_ + "out_proj.weight"), D, D, D, n,
+                    dbias=gv(a_ + "out_proj.bias"))
+        self._gemm(dy, ldy, 0, att.out_proj.weight, D, 0, w.do, D, n, D, D, st=st)
+        dv = w.do
+        if drop_p > 0:
+            dv = w.dv
+            _lib.call("ncf_dropout_rows", ptr(w.do), n, D, D // H, drop_p, seed, ptr(dv), None, st)
+        self._wgrad(w, dv, D, w.xi, D, gv(a_ + "v_proj.weight"), D, D, D, n,
+                    dbias=gv(a_ + "v_proj.bias"))
+        side = self.fork(dev, 1)
+        with torch.cuda.stream(side[0]):
+            w.run_wgrads(_lib.stream_ptr(dev), slot=1)
+        joins.append(side[0])
+        self._gemm(dv, D, 0, att.v_proj.weight, D, 0, w.dxi, D, n, D, D, st=st)
+        # (q_proj.weight, q_proj.bias, k_proj.weight, k_proj.bias: one contiguous slice of the
+        # flat gradient buffer, dense_params' order)
+        o0 = self.offsets[a_ + "q_proj.weight"][0]
+        o1, n1, _ = self.offsets[a_ + "k_proj.bias"]
+        _lib.call("ncf_fill_2d", self.gptr(a_ + "q_proj.weight"), 1, o1 + n1 - o0, o1 + n1 - o0,
+                  0.0, st)
+        _lib.call("ncf_fill_2d", ptr(w.dxu), n, D, D, 0.0, st)
+
+    def _hour_scale_bwd(self, w, hb, iid, temporal, st):
+        """The item scale s = 1 + f tp backwards (hour_bwd.hip): g_imf, g_xi become the gradients
+        w.r.t. the unscaled LN'd item rows (in place, what the embedding backward takes),
+        dtp = f (g_imf ⊙ y_i + g_xi ⊙ z_i); dte = dX0[:, D:] + dtp W_p (+ dtp when T == D);
+        dHourE[h] = the sum of dte over the rows of hour h."""
+        m = self.model
+        n, D, T = w.g.n, w.g.D, hb["T"]
+        pp = self.pp()
+        _lib.call("ncf_item_scale_bwd", ptr(iid), n, pp["t_mf_item"], pp["t_mlp_item"],
+                  m.num_products, D, pp["mf_norm.weight"], pp["mf_norm.bias"],
+                  pp["mlp_norm.weight"], pp["mlp_norm.bias"], LN_EPS, ptr(temporal["tp"]),
+                  float(temporal["f"]), ptr(w.dimf), ptr(w.dxi), ptr(hb["dtp"]), ptr(w.err), st)
+        dte = hb["dyt"].data_ptr() + 4 * D      # the tower part, in place at ld = D + T
+        w_p = temporal.get("w_p")
+        add = None
+        if w_p is not None:     # += dtp [n, D] · W_p [D, T]
+            _lib.call("ncf_gemm_f32", n, T, D, ptr(hb["dtp"]), D, 0, ptr(w_p), T, 0, dte, D + T,
+                      None, 2, st)
+        else:
+            add = hb["dtp"]
+        _lib.call("ncf_hour_grad", ptr(temporal["hour"]), n, dte, D + T, ptr(add), D, T,
+                  ptr(hb["dhour"]), ptr(hb["parts"]), hb["parts"].numel(), st)
 
     # ------------------------------------------------------------------ optimizer
     def table_state_tensors(self):

@@ -15,6 +15,11 @@ from .engine import LN_EPS
 from .sparse import gather_rows
 
 
+# Batch rows per first-stage workgroup of ncf_hour_grad (hour_bwd.hip NCF_HOUR_CHUNK): the piece
+# length its ordered reduction is cut at (tests size their batches by it)
+HOUR_GRAD_CHUNK = 128
+
+
 def _require_cuda(t):
     if not t.is_cuda:
         raise RuntimeError("ncf_amd ops run on the MI355X only (no CPU fallback)")
@@ -251,18 +256,39 @@ def forward_simple_hour(model, user_ids, product_ids, hour, projection=None, see
     projects it with a FRESH randomly initialised nn.Linear(T, D) on every call (:436-442) — done
     the same way here (torch's default init on the model's device) unless ``projection`` (an
     nn.Linear or (weight, bias)) is given; both item rows are scaled by (1 + 0.3 * proj) (:444,
-    :456-458, fused into the gather kernel) and the MLP input is [attention ‖ te] (:467-468)."""
+    :456-458, fused into the gather kernel) and the MLP input is [attention ‖ te] (:467-468).
+
+    With ``model.hour_backward = True``, the model in train() mode, gradients enabled and some
+    parameter requiring grad, the result is attached to autograd (architecture.
+    _NCFHourTrainFunction): the same forward values as the no-grad call with the same
+    ``seed`` and ``projection``.  An nn.Linear ``projection`` whose parameters require grad then
+    receives ``.grad``; a (weight, bias) tuple, and the fresh projection, are constants."""
     eng = model._engine
     dev = eng._check_device()
     m = model
     D, T = m.mlp_embedding_dim, m.temporal_dim
-    hour = hour.to(device=dev, dtype=torch.int64).contiguous()
-    te = gather_rows(m.temporal_encoding.hour_embed.weight, hour)
+    hour = hour.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    if T in (16, 32, 64, 128, 256):
+        te = gather_rows(m.temporal_encoding.hour_embed.weight, hour)
+    else:       # (a temporal width the row gather has no lane layout for)
+        te = torch.empty(hour.numel(), T, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.call("ncf_hour_rows", ptr(hour), hour.numel(),
+                  ptr(m.temporal_encoding.hour_embed.weight.detach()), T, ptr(te), ptr(err),
+                  _lib.stream_ptr(dev))
+        if int(err.item()):
+            raise IndexError("embedding id out of range")
     n = te.shape[0]
+    w_p = proj = None
     if T != m.mf_embedding_dim:
         if projection is None:
             projection = torch.nn.Linear(T, m.mf_embedding_dim, device=dev)
-        w_p, b_p = projection if isinstance(projection, tuple) else (projection.weight, projection.bias)
+        if isinstance(projection, tuple):
+            w_p, b_p = projection
+        else:
+            w_p, b_p = projection.weight, projection.bias
+            if w_p.requires_grad or (b_p is not None and b_p.requires_grad):
+                proj = projection
         w_p = w_p.detach().to(device=dev, dtype=torch.float32).contiguous()
         b_p = b_p.detach().to(device=dev, dtype=torch.float32).contiguous()
         tp = torch.empty(n, m.mf_embedding_dim, device=dev)
@@ -272,10 +298,28 @@ def forward_simple_hour(model, user_ids, product_ids, hour, projection=None, see
         tp = te
     # training mode (the reference's nn.Dropout layers active, :458-473): the attention's
     # dropout on its single-key weight and the tower's after every LayerNorm, from the package's
-    # dropout stream (a fresh seed per call unless given); no backward through this path
+    # dropout stream (a fresh seed per call unless given)
     drop_p = float(m.dropout) if m.training else 0.0
     if drop_p > 0 and seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    if (m.training and torch.is_grad_enabled() and getattr(m, "hour_backward", False)
+            and any(p.requires_grad for p in m.parameters())):
+        from .architecture import _NCFHourTrainFunction
+        uid = user_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        iid = product_ids.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        if uid.numel() != n or iid.numel() != n:
+            raise ValueError("forward_simple: user_ids, product_ids and hour differ in length")
+        ctx = {"tp": tp, "te": te, "hour": hour, "f": 0.3, "proj": proj,
+               "w_p": w_p if T != m.mf_embedding_dim else None}
+        out = _NCFHourTrainFunction.apply(eng, uid, iid, drop_p, seed or 0, ctx, m._anchor)
+        v = getattr(m, "validate_ids", True)
+        if v:
+            ws = eng.ws[(n, 1, True)]
+            if v != "sync":
+                eng.check_ids_async(ws)      # no host sync inside the training loop
+            else:
+                eng.check_ids(ws)
+        return out
     w = eng.forward(user_ids, product_ids, 1, False, drop_p, seed or 0, temporal=(tp, 0.3, te))
     eng.check_ids(w)
     return w.prob.clone()

@@ -208,6 +208,10 @@ class StepTapes:
         advance), replayed or recorded; False when the caller must call run() itself."""
         if not self.usable() or not self._horizon():
             return False
+        if getattr(w, "no_tape", False):
+            # a forward_simple(hour) training step shares the (n, 1) workspace of the plain
+            # forward_simple step: it runs eagerly in every phase (DESIGN §17)
+            return False
         # (betas / eps / weight decay are launch arguments here: checked with the addresses)
         if self.sig is None or self._signature(5) != self.sig[:5]:
             self.entries.clear()
