@@ -816,6 +816,38 @@ int ncf_score_select_rescored_excl(const int32_t* user_list, int64_t n_users,
 int ncf_score_merge(const float* cand_score, const int64_t* cand_item, int64_t n_users, int64_t L,
                     int K, float* out_score, int64_t* out_item, void* stream);
 
+/* ---- exact rank of a held-out item over the whole catalogue (leave-one-out evaluation;
+ * csrc/rank.hip) -- for queried row r with held-out item h = held[r] and fp32 logits
+ * s_j = queries[r] . items[j] + item_bias[j]:
+ *   count[r] = #{ j in [0, n_items), j not in seen(user_ids[r]) : beats(j) },
+ *   beats(j) = (s_j > s_h and j != h) or (s_j == s_h and j < h)
+ * the 0-based place of h in the (logit desc, item id asc) order of the top-K pipeline.  All three
+ * entry points compute a logit by the same arithmetic (v_mfma_f32_32x32x2_f32 in one k order,
+ * then + bias), so equal operands give equal bits and bit-identical items tie exactly.  dim 64 or
+ * 128 (rows as ncf_score_queries / the item index pad them); n_items < 2^31; queries and items
+ * 16-byte aligned; nothing is allocated and the host is never synchronised.
+ * ncf_rank_pair_logits: out[e] = s of (row rows[e], or e when rows is NULL; item pair_items[e]),
+ *   32 pairs per wave on the diagonal of a 32 x 32 tile.  A row or item out of range ORs 4 into
+ *   err_flag (may be NULL) and takes row 0, item 0.
+ * ncf_rank_scan: count[r] += #{ j in [0, n_items) : beats(j) } with target[r] = s_h from
+ *   ncf_rank_pair_logits; count is zeroed by the caller; one integer atomic per row and item
+ *   block of items_per_block items (a multiple of 32; 0: chosen to fill the chip).
+ * ncf_rank_seen_correct: count[r] -= #{ j in seen(user_ids[r]) : beats(j) }, after the scan on
+ *   the same stream; seen_offsets / seen_items: the CSR of ncf_score_select_excl (a user id
+ *   outside [0, num_users) has no list; a seen id outside the catalogue is skipped, err 4). */
+int ncf_rank_pair_logits(const float* queries, int64_t n_queries, const int32_t* rows,
+                         const int32_t* pair_items, int64_t n_pairs, const float* items,
+                         const float* item_bias, int64_t n_items, int64_t dim, float* out,
+                         int* err_flag, void* stream);
+int ncf_rank_scan(const float* queries, int64_t n_rows, const float* items,
+                  const float* item_bias, int64_t n_items, int64_t dim, const float* target,
+                  const int32_t* held, int64_t items_per_block, int32_t* count, void* stream);
+int ncf_rank_seen_correct(const float* queries, int64_t n_rows, const int32_t* held,
+                          const float* target, const int64_t* user_ids, int64_t num_users,
+                          const int64_t* seen_offsets, const int32_t* seen_items,
+                          const float* items, const float* item_bias, int64_t n_items,
+                          int64_t dim, int32_t* count, int* err_flag, void* stream);
+
 /* ---- exact nearest-product search over the exported embeddings (api.py:63-73: the query the
  * Tree-AH index of setup_tree_ah_endpoint.py:25-32 answers approximately; csrc/neighbors.hip) --
  * similarity(q, i) = fp32 dot product of query q (divided by its L2 norm first when normalize

@@ -13,7 +13,8 @@ from .sparse import (EmbeddingBagCollection, EmbeddingBagConfig, JaggedTensor,  
                      KeyedJaggedTensor, PoolingType, pool_rows)
 from .architecture import (AdvancedNCF, CategoryHierarchy, MultiHeadAttention,  # noqa: F401
                            TemporalEncoding)
-from .scoring import SeenItems  # noqa: F401
+from .scoring import SeenItems, score_rank  # noqa: F401
+from .metrics import ranking_report  # noqa: F401
 from .neighbors import ProductSearch  # noqa: F401
 
 __version__ = "1.0.0"

@@ -208,6 +208,9 @@ SIGNATURES = {
     "ncf_score_select_rescored_excl": (I32, [P, I64, P, P, I64, I32, P, P, P, I64, P, F32, P, P, P,
                                              P, P, P, I64, P, P, P, P]),
     "ncf_score_merge": (I32, [P, P, I64, I64, I32, P, P, P]),
+    "ncf_rank_pair_logits": (I32, [P, I64, P, P, I64, P, P, I64, I64, P, P, P]),
+    "ncf_rank_scan": (I32, [P, I64, P, P, I64, I64, P, P, I64, P, P]),
+    "ncf_rank_seen_correct": (I32, [P, I64, P, P, P, I64, P, P, P, P, I64, I64, P, P, P]),
     "ncf_nn_scan": (I32, [P, I64, I32, P, I64, I64, P, P, P, I64, I64, I32, P, P, P]),
     "ncf_temporal_fwd": (I32, [P, P, P, P, I64, P, P, P, P, I64, I64, P, P, P]),
     "ncf_temporal_bwd": (I32, [P, P, P, I64, P, I64, P, P, P, P]),

@@ -11,7 +11,9 @@ column asc (torch.topk / torch.sort leave it unspecified).  GPU only (no CPU fal
 
 ``full_ranking_metrics`` is the leave-one-out protocol over the whole catalogue instead of over
 sampled negatives: the held-out item's place among all the items the user has not seen
-(``scoring.score_topk(exclude=...)``).
+(``scoring.score_topk(exclude=...)``).  ``ranking_report`` is the same protocol from the exact
+place of every held-out item (``scoring.score_rank``): every k in one pass, untruncated MRR, mean
+rank and per-user AUC.
 """
 import warnings
 from typing import Dict, List, Optional
@@ -109,3 +111,38 @@ def full_ranking_metrics(model, users: torch.Tensor, heldout_items: torch.Tensor
     mrr = torch.where(found, 1.0 / (place + 1.0), torch.zeros_like(place)).sum() / n
     hr, ndcg, mrr = torch.stack([hr, ndcg, mrr]).tolist()
     return {f"hr@{k}": hr, f"ndcg@{k}": ndcg, f"mrr@{k}": mrr}
+
+
+def ranking_report(model, users: torch.Tensor, heldout_items: torch.Tensor,
+                   k_values=(1, 5, 10), exclude=None, index=None, hour=None) -> Dict[str, float]:
+    """The leave-one-out protocol of ``full_ranking_metrics`` from the exact place of every
+    held-out item (``scoring.score_rank``: one counting scan of the catalogue, no top-k lists):
+    ``hr@k`` / ``ndcg@k`` / ``mrr@k`` for every k of ``k_values`` by the same formulas, and what a
+    top-k list cannot give: ``mrr`` (untruncated), ``mean_rank`` (the mean of place + 1) and
+    ``auc`` (the mean of 1 - place / (candidates - 1), the share of a user's other unseen items
+    ranked below the held-out one, over the users with more than one candidate; nan without
+    any).  ``exclude`` / ``index`` / ``hour`` as in ``full_ranking_metrics``."""
+    from .scoring import score_rank
+    ks = sorted({int(k) for k in k_values})
+    if ks and ks[0] < 1:
+        raise ValueError("ranking_report: k must be >= 1")
+    place, cand = score_rank(model, users, heldout_items, index, exclude=exclude, hour=hour)
+    pl = place.to(torch.float64)
+    n = max(1, pl.numel())
+    zero = torch.zeros_like(pl)
+    sums = []
+    for k in ks:
+        found = place < k
+        sums += [found.to(torch.float64).sum() / n,
+                 torch.where(found, 1.0 / torch.log2(pl + 2.0), zero).sum() / n,
+                 torch.where(found, 1.0 / (pl + 1.0), zero).sum() / n]
+    many = cand > 1
+    auc = torch.where(many, 1.0 - pl / (cand - 1).clamp_min(1).to(torch.float64), zero).sum() / \
+        many.to(torch.float64).sum()      # (0 / 0 = nan: no user with two candidates)
+    sums += [(1.0 / (pl + 1.0)).sum() / n, (pl + 1.0).sum() / n, auc]
+    vals = torch.stack(sums).tolist()
+    out: Dict[str, float] = {}
+    for j, k in enumerate(ks):
+        out[f"hr@{k}"], out[f"ndcg@{k}"], out[f"mrr@{k}"] = vals[3 * j:3 * j + 3]
+    out["mrr"], out["mean_rank"], out["auc"] = vals[-3:]
+    return out

@@ -34,6 +34,10 @@ every call (architecture.py:437-442); a ranking needs one fixed projection, give
 candidates in the user's list (a CSR keyed by user id) and verifies the rest against the collect
 threshold; a user whose seen items reach into the top k is re-run from a threshold that leaves
 k unseen items at or above it (``_TopKRun.redo_excluded``).
+
+``score_rank`` is the evaluation side of the same scorer: the exact 0-based place of one held-out
+item per user among the items the user has not seen, by the top-k order, from one fp32 MFMA scan
+that counts instead of collecting (csrc/rank.hip; no k, no thresholds, no re-runs).
 """
 from types import SimpleNamespace
 from typing import Optional, Tuple
@@ -813,6 +817,135 @@ def score_topk(model, user_ids: torch.Tensor, k: int = 10, index: Optional[ItemI
         scores[pos] = s
         items[pos] = i
     return scores, items
+
+
+def _check_rank(user_ids, item_ids, num_products: int, exclude=None, index=None):
+    """``score_rank``'s arguments before any launch (torch ops on the tensors' own devices: no
+    GPU needed): one held-out item per user (ValueError), item ids inside the catalogue
+    (IndexError), no held-out item inside its user's history (ValueError, the rule of
+    ``full_ranking_metrics``), and an index over the whole catalogue (ValueError for a subset
+    index: a place among a shard's items is not the place in the catalogue)."""
+    if user_ids.numel() != item_ids.numel():
+        raise ValueError(f"score_rank: {user_ids.numel()} users for {item_ids.numel()} held-out "
+                         "items (one held-out item per user)")
+    if item_ids.is_floating_point() or item_ids.dtype == torch.bool:
+        raise TypeError("score_rank: item ids must be integers")
+    if index is not None and index.ids is not None:
+        raise ValueError("score_rank: the index covers a subset of the catalogue; the place of "
+                         "an item is counted over all of it")
+    if item_ids.numel() and (int(item_ids.min()) < 0 or int(item_ids.max()) >= num_products):
+        raise IndexError("score_rank: item id out of range of the catalogue")
+    if exclude is not None and item_ids.numel() and \
+            bool(exclude.contains(user_ids, item_ids).any()):
+        raise ValueError("score_rank: a held-out item is in its user's history")
+
+
+def _rank_places(q, p, bias, held, *, seen: Optional[SeenItems] = None, users=None,
+                 items_per_block: int = 0, err=None) -> torch.Tensor:
+    """The rank kernels (csrc/rank.hip) on raw device tensors: ``q [n, qd]`` query rows,
+    ``p [I, qd]`` item rows, ``bias [I]``, ``held [n]`` item ids -> int64 ``[n]``, the number of
+    items that beat each row's held-out item, without those in ``seen`` of ``users[r]``.
+    ``items_per_block``: the scan's item split (0: chosen by the kernel's entry point).  ``err``:
+    the int32 flag word the kernels OR 4 into for an id outside ``[0, I)``.  No host sync."""
+    n, qd = q.shape
+    I = p.shape[0]
+    dev = q.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev)
+    if (seen is None) != (users is None):
+        raise ValueError("_rank_places: seen and users go together")
+    q, p, bias = q.contiguous(), p.contiguous(), bias.contiguous()
+    held32 = held.to(device=dev, dtype=torch.int32).contiguous()
+    target = torch.empty(n, device=dev)
+    count = torch.zeros(n, dtype=torch.int32, device=dev)
+    st = _lib.stream_ptr(dev)
+    _lib.call("ncf_rank_pair_logits", ptr(q), n, None, ptr(held32), n, ptr(p), ptr(bias), I, qd,
+              ptr(target), ptr(err), st)
+    _lib.call("ncf_rank_scan", ptr(q), n, ptr(p), ptr(bias), I, qd, ptr(target), ptr(held32),
+              int(items_per_block), ptr(count), st)
+    if seen is not None:
+        uid = users.to(device=dev, dtype=torch.int64).contiguous()
+        _lib.call("ncf_rank_seen_correct", ptr(q), n, ptr(held32), ptr(target), ptr(uid),
+                  seen.num_users, ptr(seen.offsets), ptr(seen.items), ptr(p), ptr(bias), I, qd,
+                  ptr(count), ptr(err), st)
+    return count.to(torch.int64)
+
+
+def score_rank(model, user_ids: torch.Tensor, item_ids: torch.Tensor,
+               index: Optional[ItemIndex] = None, *, exclude: Optional[SeenItems] = None,
+               hour=None, projection=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exact place of one held-out item per user among everything the user has not seen:
+    ``place[r] = #{j not in seen(u_r): beats(j)}``, 0-based (``place < k``: in the top k), where
+    ``beats(j) = (s_j > s_h and j != h) or (s_j == s_h and j < h)`` is ``score_topk``'s order
+    (score desc, item id asc) on the fp32 logits of its factorised scorer.  Returns ``(place
+    int64 [n], candidates int64 [n])``, ``candidates = I - len(seen(u_r))``.  One MFMA scan of the
+    catalogue that counts (csrc/rank.hip): no k, no candidate lists, no re-runs; HR / NDCG / MRR
+    at any k, mean rank and AUC follow from ``place`` (``metrics.ranking_report``).  ``index``,
+    ``exclude``, ``hour`` and ``projection`` as in ``score_topk``; the index must cover the whole
+    catalogue, and a held-out item inside its user's history is refused."""
+    user_ids, item_ids = user_ids.reshape(-1), item_ids.reshape(-1)
+    _check_exclude(exclude, model.num_users, model.num_products)
+    hour = _check_hour(hour, user_ids.numel())
+    _check_rank(user_ids, item_ids, model.num_products, exclude, index)
+    if index is None:
+        index = ItemIndex(model, projection=projection)
+    else:
+        if projection is not None and not index.owns_projection(projection):
+            raise ValueError("score_rank: index was built with another projection; pass the "
+                             "projection to ItemIndex and leave it out here")
+        if not index.valid_for(model):   # parameters changed since the index was built
+            index = ItemIndex(model, projection=index.projection)
+    dev = index.p.device
+    _check_exclude(exclude, model.num_users, model.num_products, dev)
+    uid = user_ids.to(device=dev, dtype=torch.int64).contiguous()
+    held = item_ids.to(device=dev, dtype=torch.int64).contiguous()
+    n = uid.numel()
+    if n == 0:
+        return (torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.int64, device=dev))
+    I, qd = index.p.shape
+    st = _lib.stream_ptr(dev)
+    table = model.mf_embedding_collection.embedding_bags["user_id"].weight
+    q = torch.empty(n, qd, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    seen = dict(seen=exclude, users=uid) if exclude is not None else {}
+    if hour is None:
+        _lib.call("ncf_score_queries", ptr(uid), n, ptr(table), model.num_users,
+                  model.mf_embedding_dim, ptr(model.mf_norm.weight), ptr(model.mf_norm.bias),
+                  LN_EPS, ptr(model.mf_output.weight), ptr(model.final[0].weight), ptr(q),
+                  ptr(err), st)
+        place = _rank_places(q, index.p, index.bias, held, err=err, **seen)
+    else:
+        # one query launch for every row (the kernel scales row r by its own hour's s_h); the
+        # item bias is per hour, so the rows are ranked in groups of one hour
+        hours = hour.to(device=dev, dtype=torch.int64).contiguous() \
+            if isinstance(hour, torch.Tensor) else torch.full((n,), hour, dtype=torch.int64,
+                                                              device=dev)
+        _lib.call("ncf_score_queries_hour", ptr(uid), ptr(hours), n, ptr(table), model.num_users,
+                  model.mf_embedding_dim, ptr(model.mf_norm.weight), ptr(model.mf_norm.bias),
+                  LN_EPS, ptr(model.mf_output.weight), ptr(model.final[0].weight),
+                  ptr(index.hour_table()), ptr(q), ptr(err), st)
+        groups = group_by_hour(hours)
+        place = torch.empty(n, dtype=torch.int64, device=dev)
+        for h, pos in groups:
+            # (an hour out of range: ranked at hour 0 and flagged by the kernel, which raises)
+            bias_h = index.hour_bias(h if 0 <= h < 24 else 0)
+            if len(groups) == 1:
+                place = _rank_places(q, index.p, bias_h, held, err=err, **seen)
+            else:
+                sub = dict(seen=exclude, users=uid[pos]) if exclude is not None else {}
+                place[pos] = _rank_places(q[pos], index.p, bias_h, held[pos], err=err, **sub)
+    flags = int(err.item())
+    if flags & 1:
+        raise IndexError("score_rank: user id out of range of the embedding table")
+    if flags & 2:
+        raise IndexError("score_rank: hour outside [0, 24)")
+    if flags & 4:
+        raise IndexError("score_rank: item id out of range of the catalogue")
+    candidates = torch.full((n,), I, dtype=torch.int64, device=dev)
+    if exclude is not None:
+        candidates -= exclude.lengths[uid]
+    return place, candidates
 
 
 class GraphedScorer:

@@ -1,0 +1,348 @@
+"""scoring.score_rank / metrics.ranking_report (csrc/rank.hip): the exact place of each user's
+held-out item among the items the user has not seen.
+
+1. integer-valued data, where every product and partial sum is exact in fp32 in any order: equal
+   to the float64 reference (tests/rank_ref.py) with zero tolerance;
+2. real-valued data: one arithmetic for the held-out item's logit, the scan's and the seen
+   items' (copies of an item tie with it exactly, wherever they sit);
+3. end to end inside the float64 oracle's bracket at the project's scoring tolerance of 1e-6;
+4. at an hour of day, against score_topk(hour=)'s own lists;
+5. ranking_report against its formulas and against full_ranking_metrics."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import _ncf_pkg
+from oracle import ncf_oracle as O
+from tests import rank_ref as R
+
+pytestmark = pytest.mark.gpu
+ncf = _ncf_pkg.load()
+from ncf_amd import metrics, scoring  # noqa: E402
+from ncf_amd.scoring import ItemIndex, SeenItems, score_rank, score_topk  # noqa: E402
+DEV = torch.device("cuda:0")
+
+
+def _seen(lists, U, I, dev=DEV):
+    """SeenItems from one sorted list of item ids per user."""
+    off = np.zeros(U + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(x) for x in lists])
+    flat = np.array([j for x in lists for j in x], dtype=np.int32)
+    return SeenItems.from_csr(torch.from_numpy(off), torch.from_numpy(flat), I).to(dev)
+
+
+# ---- 1. exact, integer-valued, through _rank_places
+
+N1, I1, U1 = 300, 4099, 40   # two row blocks + a partial wave; a 3-item tail tile
+
+
+@functools.lru_cache(maxsize=None)
+def _int_world(D):
+    """q, p in {-4..4}, bias in {-2, -1.75, .., 2}: logits exact in fp32; their float64 values,
+    the histories and the reference places, computed once per D."""
+    rng = np.random.default_rng(100 + D)
+    q = rng.integers(-4, 5, (N1, D)).astype(np.float64)
+    p = rng.integers(-4, 5, (I1, D)).astype(np.float64)
+    bias = rng.integers(-8, 9, I1) * 0.25
+    logits = q @ p.T + bias[None, :]
+    # users 0..37 repeat with different held-out items; user 38 has no history; user 39 has seen
+    # every item that beats theirs
+    users = np.concatenate([rng.integers(0, 38, N1 - 2), [38, 39]])
+    held = rng.integers(0, I1, N1)
+    lists = []
+    for u in range(U1):
+        mine = set(held[users == u].tolist())
+        if u == 38:
+            lists.append([])
+        elif u == 39:
+            r = N1 - 1
+            h = int(held[r])
+            lists.append([j for j in range(I1) if R.beats(logits[r, j], j, logits[r, h], h)])
+        else:
+            got = set(rng.integers(0, I1, rng.integers(0, 51)).tolist()) - mine
+            lists.append(sorted(got))
+    seen_rows = [lists[u] for u in users]
+    assert len(lists[39]) > 64      # (several 32-item chunks of the seen walk)
+    ref = R.places(logits, held)
+    ref_seen = R.places(logits, held, seen_rows)
+    assert ref_seen[N1 - 1] == 0 and ref[N1 - 1] == len(lists[39])
+    # the data ties on its own: many rows have another item at exactly the held-out logit
+    ties = sum(int((logits[r] == logits[r, held[r]]).sum()) > 1 for r in range(N1))
+    assert ties > N1 // 2
+    return dict(q=q, p=p, bias=bias, users=users, held=held, lists=lists, ref=ref,
+                ref_seen=ref_seen)
+
+
+@pytest.mark.parametrize("with_seen", [False, True])
+@pytest.mark.parametrize("items_per_block", [0, 1024])
+@pytest.mark.parametrize("D", [64, 128])
+def test_exact_integer_valued(D, items_per_block, with_seen):
+    w = _int_world(D)
+    f = lambda a: torch.from_numpy(a).to(device=DEV, dtype=torch.float32)   # noqa: E731
+    held = torch.from_numpy(w["held"]).to(DEV)
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    kw = dict(seen=_seen(w["lists"], U1, I1), users=torch.from_numpy(w["users"]).to(DEV)) \
+        if with_seen else {}
+    place = scoring._rank_places(f(w["q"]), f(w["p"]), f(w["bias"]), held,
+                                 items_per_block=items_per_block, err=err, **kw)
+    assert place.dtype == torch.int64 and place.shape == (N1,)
+    want = w["ref_seen"] if with_seen else w["ref"]
+    assert place.cpu().numpy().tolist() == want.tolist()
+    assert int(err.item()) == 0
+
+
+def test_rank_places_flags_an_item_outside_the_catalogue():
+    w = _int_world(64)
+    f = lambda a: torch.from_numpy(a).to(device=DEV, dtype=torch.float32)   # noqa: E731
+    held = torch.from_numpy(w["held"][:5].copy()).to(DEV)
+    held[3] = I1
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    scoring._rank_places(f(w["q"][:5]), f(w["p"]), f(w["bias"]), held, err=err)
+    assert int(err.item()) == 4
+
+
+# ---- 3 (set up first: 2 and 5 share its models). End to end against the float64 oracle
+
+U3, I3, N3 = 64, 2500, 37
+CASES = {
+    "default": (5, (), 3),
+    "narrow": (7, (16, 16, 32, [64, 32], 1), 2),
+    # (seed 5 meets the cap at D = 128 as well: 1 ambiguous row on the CPU, no other seed tried)
+    "d128": (5, (128, 128), 3),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _world(case):
+    seed, extra, n_layers = CASES[case]
+    torch.manual_seed(seed)
+    m = ncf.AdvancedNCF(U3, I3, 5, 24, *extra).to(DEV).eval()
+    g = torch.Generator().manual_seed(17)
+    users = torch.randint(0, U3, (N3,), generator=g)
+    held = torch.randint(0, I3, (N3,), generator=g)
+    # random histories (0-40 items per user, never a held-out item of that user)
+    lists = []
+    for u in range(U3):
+        k = int(torch.randint(0, 41, (1,), generator=g))
+        it = set(torch.randint(0, I3, (k,), generator=g).tolist())
+        lists.append(sorted(it - set(held[users == u].tolist())))
+    p = {k: v.detach().cpu().double() for k, v in m.state_dict().items()}
+    prob = O.score_factorised(p, users, torch.arange(I3), temporal_dim=32, n_layers=n_layers)
+    return dict(m=m, users=users, held=held, lists=lists, prob=prob.numpy(), idx=ItemIndex(m))
+
+
+def _bracket(w, with_seen):
+    """lo = #{p_j > p_h + 1e-6}, hi = #{j != h : p_j >= p_h - 1e-6} over the unseen items, in the
+    oracle's float64 probabilities."""
+    prob, users, held = w["prob"], w["users"], w["held"]
+    lo, hi = np.zeros(N3, dtype=np.int64), np.zeros(N3, dtype=np.int64)
+    for r in range(N3):
+        h = int(held[r])
+        keep = np.ones(I3, dtype=bool)
+        if with_seen:
+            keep[np.array(w["lists"][int(users[r])], dtype=np.int64)] = False
+        a = (prob[r] > prob[r, h] + 1e-6) & keep
+        b = (prob[r] >= prob[r, h] - 1e-6) & keep
+        b[h] = False
+        lo[r], hi[r] = a.sum(), b.sum()
+    return lo, hi
+
+
+@pytest.mark.parametrize("case,with_seen", [("default", False), ("narrow", False),
+                                            ("d128", False), ("default", True)])
+def test_vs_oracle_bracket(case, with_seen):
+    w = _world(case)
+    lo, hi = _bracket(w, with_seen)
+    # a condition on the inputs, from the oracle alone, before the GPU result is looked at
+    assert int((lo != hi).sum()) <= 4, (lo != hi).sum()
+    ex = _seen(w["lists"], U3, I3) if with_seen else None
+    place, cand = score_rank(w["m"], w["users"], w["held"], w["idx"], exclude=ex)
+    place, cand = place.cpu().numpy(), cand.cpu().numpy()
+    print(f"{case} seen={with_seen}: ambiguous rows {int((lo != hi).sum())}, places "
+          f"{place.min()}..{place.max()}, outside the bracket "
+          f"{int(((place < lo) | (place > hi)).sum())}")
+    assert ((lo <= place) & (place <= hi)).all(), (lo, place, hi)
+    want = [I3 - (len(w["lists"][int(u)]) if with_seen else 0) for u in w["users"]]
+    assert cand.tolist() == want
+    # without an index the call builds its own: the same places
+    if case == "default" and not with_seen:
+        assert score_rank(w["m"], w["users"], w["held"])[0].cpu().numpy().tolist() == \
+            place.tolist()
+
+
+def test_empty_and_device_side_errors():
+    w = _world("default")
+    place, cand = score_rank(w["m"], torch.zeros(0, dtype=torch.int64),
+                             torch.zeros(0, dtype=torch.int64), w["idx"])
+    assert place.shape == (0,) and cand.shape == (0,) and place.dtype == torch.int64
+    with pytest.raises(IndexError, match="user id out of range"):
+        score_rank(w["m"], torch.tensor([3, U3]), torch.tensor([1, 2]), w["idx"])
+    with pytest.raises(ValueError, match="subset of the catalogue"):
+        score_rank(w["m"], torch.tensor([3]), torch.tensor([1]),
+                   ItemIndex(w["m"], items=torch.arange(100)))
+
+
+# ---- 2. bitwise consistency on real-valued data
+
+ROWS2 = (0, 5, 9, 14, 19, 23, 28, 36)    # both lane halves of the pair tile's diagonal
+
+
+@pytest.mark.parametrize("case", ["default", "d128"])
+def test_copies_of_the_heldout_item_tie_exactly(case):
+    """The held-out item copied to one lower and two higher ids, each in another 32-item tile
+    and another item block of the scan (256 items at this size): the lower copy ties and goes
+    first by its id, the higher ones tie and go behind, so the place rises by exactly 1; with the
+    lower copy in the user's history (its logit then comes from the seen walk) it is unchanged.
+    Any difference between the three computations of one logit would show as 0, 2 or 3.
+    "The index without copies" holds, at the three positions, items that beat nothing (a bias
+    of -1e30): the items that stood there before may themselves have been ahead of the held-out
+    one, and overwriting those would take them off the count."""
+    w = _world(case)
+    m, users = w["m"], w["users"]
+    idx = ItemIndex(m)
+    held = w["held"].clone()
+    for t, r in enumerate(ROWS2):
+        held[r] = 1030 + 3 * t                # block 4 (items 1024..1279)
+    p0, b0 = idx.p.clone(), idx.bias.clone()
+    for t, r in enumerate(ROWS2):
+        h = int(held[r])
+        low, high = 70 + 37 * t, (1700 + 41 * t, 2300 + 13 * t)
+        assert len({j // 256 for j in (low, h) + high}) == 4
+        assert len({j // 32 for j in (low, h) + high}) == 4
+        for j in (low,) + high:
+            idx.bias[j] = -1e30
+        base = score_rank(m, users, held, idx)[0].cpu()
+        for j in (low,) + high:
+            idx.p[j].copy_(p0[h])
+            idx.bias[j] = b0[h]
+        got = score_rank(m, users, held, idx)[0].cpu()
+        assert int(got[r]) == int(base[r]) + 1, (r, int(got[r]), int(base[r]))
+        ex = SeenItems(users[r:r + 1], torch.tensor([low]), U3, I3).to(DEV)
+        got, cand = score_rank(m, users, held, idx, exclude=ex)
+        assert int(got[r]) == int(base[r]), (r, int(got[r]), int(base[r]))
+        assert int(cand[r]) == I3 - 1
+        idx.p.copy_(p0)
+        idx.bias.copy_(b0)
+
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_identical_catalogue(D):
+    """1000 identical item rows: everything ties with everything, so the place is the held-out
+    id minus the user's seen ids below it, for every row (any q)."""
+    I, n, U = 1000, 70, 20
+    g = torch.Generator().manual_seed(3 + D)
+    q = torch.randn(n, D, generator=g)
+    p = torch.randn(1, D, generator=g).expand(I, D).contiguous()
+    bias = torch.full((I,), 0.37)
+    users = torch.randint(0, U, (n,), generator=g)
+    held = torch.randint(0, I, (n,), generator=g)
+    lists = []
+    for u in range(U):
+        it = set(torch.randint(0, I, (int(torch.randint(0, 90, (1,), generator=g)),),
+                               generator=g).tolist())
+        lists.append(sorted(it - set(held[users == u].tolist())))
+    want = [int(h) - sum(j < int(h) for j in lists[int(u)]) for u, h in zip(users, held)]
+    for ipb in (0, 1024):       # four item blocks of 256 (the entry point's choice), and one
+        place = scoring._rank_places(q.to(DEV), p.to(DEV), bias.to(DEV), held.to(DEV),
+                                     seen=_seen(lists, U, I), users=users.to(DEV),
+                                     items_per_block=ipb)
+        assert place.cpu().tolist() == want
+        place = scoring._rank_places(q.to(DEV), p.to(DEV), bias.to(DEV), held.to(DEV),
+                                     items_per_block=ipb)
+        assert place.cpu().tolist() == held.tolist()
+
+
+# ---- 4. hour
+
+@functools.lru_cache(maxsize=None)
+def _hour_world():
+    torch.manual_seed(11)
+    m = ncf.AdvancedNCF(U3, I3, 5, 24, 64, 64, 64).to(DEV).eval()   # T = D: no projection
+    g = torch.Generator().manual_seed(17)
+    users = torch.randint(0, U3, (N3,), generator=g)
+    hours = torch.randint(0, 24, (N3,), generator=g)
+    return m, users, hours, ItemIndex(m)
+
+
+@pytest.mark.parametrize("mixed", [False, True])
+def test_hour_against_topk_lists(mixed):
+    m, users, hours, idx = _hour_world()
+    hour = hours if mixed else 13
+    if mixed:
+        assert len(set(hours.tolist())) > 5
+    s, it = score_topk(m, users, 50, idx, hour=hour)
+    s, it = s.cpu().double().numpy(), it.cpu().numpy()
+    pos = np.array([(7 * r) % 49 for r in range(N3)])
+    held = torch.from_numpy(it[np.arange(N3), pos])
+    place = score_rank(m, users, held, idx, hour=hour)[0].cpu().numpy()
+    clear = [r for r in range(N3)
+             if (np.abs(np.delete(s[r], pos[r]) - s[r, pos[r]]) > 1e-6).all()]
+    assert len(clear) >= 5
+    assert place[clear].tolist() == pos[clear].tolist()
+    # the hour matters: without it the same items stand elsewhere
+    plain = score_rank(m, users, held, idx)[0].cpu().numpy()
+    assert (plain != place).any()
+    if mixed:
+        with pytest.raises(IndexError, match="hour outside"):
+            bad = hours.clone()
+            bad[4] = 24
+            score_rank(m, users, held, idx, hour=bad)
+
+
+# ---- 5. ranking_report
+
+def _report_np(place, cand, ks):
+    pl = place.astype(np.float64)
+    out = {}
+    for k in ks:
+        f = place < k
+        out[f"hr@{k}"] = f.mean()
+        out[f"ndcg@{k}"] = np.where(f, 1.0 / np.log2(pl + 2.0), 0.0).mean()
+        out[f"mrr@{k}"] = np.where(f, 1.0 / (pl + 1.0), 0.0).mean()
+    out["mrr"] = (1.0 / (pl + 1.0)).mean()
+    out["mean_rank"] = (pl + 1.0).mean()
+    many = cand > 1
+    out["auc"] = (1.0 - pl[many] / (cand[many] - 1.0)).mean()
+    return out
+
+
+@pytest.mark.parametrize("with_seen", [False, True])
+def test_ranking_report_formulas(with_seen):
+    w = _world("narrow")
+    ex = _seen(w["lists"], U3, I3) if with_seen else None
+    ks = (1, 5, 10, 100, 1000)
+    rep = metrics.ranking_report(w["m"], w["users"], w["held"], ks, exclude=ex, index=w["idx"])
+    place, cand = score_rank(w["m"], w["users"], w["held"], w["idx"], exclude=ex)
+    want = _report_np(place.cpu().numpy(), cand.cpu().numpy(), ks)
+    assert set(rep) == set(want)
+    for k, v in want.items():
+        assert abs(rep[k] - v) <= 1e-12, (k, rep[k], v)
+    assert 0.0 < rep["mrr@1000"] < rep["mrr"] and rep["hr@1"] <= rep["hr@1000"]
+    assert metrics.ranking_report(w["m"], w["users"], w["held"], ks[::-1], exclude=ex,
+                                  index=w["idx"]) == rep
+
+
+@pytest.mark.parametrize("case,from_top", [("default", False), ("narrow", False),
+                                           ("default", True)])
+def test_ranking_report_agrees_with_full_ranking_metrics(case, from_top):
+    """On the rows whose oracle bracket is one place wide (test_vs_oracle_bracket's
+    unambiguous rows) both protocols see the same place.  ``from_top``: the held-out items taken
+    from the users' own top-20 lists instead, so that k = 10 has hits and misses to count."""
+    w = _world(case)
+    m, users, idx, held = w["m"], w["users"], w["idx"], w["held"]
+    if from_top:
+        top = score_topk(m, users, 20, idx)[1].cpu()
+        held = top[torch.arange(N3), torch.arange(N3) % 20]
+        w = dict(w, held=held)
+    lo, hi = _bracket(w, False)
+    rows = torch.from_numpy(np.nonzero(lo == hi)[0])
+    assert rows.numel() >= (5 if from_top else N3 - 4)
+    rep = metrics.ranking_report(m, users[rows], held[rows], (10,), index=idx)
+    full = metrics.full_ranking_metrics(m, users[rows], held[rows], 10, index=idx)
+    print(f"{case} from_top={from_top}: {rows.numel()} rows, {full}")
+    if from_top:
+        assert 0.0 < full["hr@10"] < 1.0
+    for k in ("hr@10", "ndcg@10", "mrr@10"):
+        assert abs(rep[k] - full[k]) <= 1e-12, (k, rep[k], full[k])
