@@ -762,26 +762,23 @@ int ncf_score_collect_split(const float* queries, const int32_t* user_list, int6
  * terms = 2: the scan takes only x0 + x1 of each operand (three products a0b0 + a0b1 + a1b0):
  * its logits are within 1e-4 * |q_u| * max_i |p_i| of fp32, so the thresholds are first lowered
  * by that (ncf_score_margin, with max_i |p_i| from ncf_score_item_norm_max) and the candidates'
- * logits recomputed in fp32 by ncf_score_select_rescored. */
+ * logits recomputed in fp32 by ncf_score_select's re-scoring. */
 int ncf_score_item_norm_max(const float* items, int64_t n_items, int64_t dim, uint32_t* out_bits,
                             void* stream);
 int ncf_score_margin(const float* queries, const int32_t* user_list, int64_t n_users, int64_t dim,
                      const uint32_t* item_norm_max, float c, float* thr, void* stream);
-int ncf_score_select_rescored(const int32_t* user_list, int64_t n_users, const uint32_t* count,
-                              const ncf_score_cand* cand, int64_t cap, int K, const float* queries, const float* items,
-                              const float* item_bias, int64_t dim, const uint32_t* item_norm_max,
-                              float c, float* out_score, int64_t* out_item, float* thr,
-                              uint32_t* overflow, const float* thr_check, void* stream);
-/* thr_check (may be NULL): per user, a threshold T the collect was run below (its rank-j sample
+/* The per-user select, with two optional argument groups, each all-NULL (dim and c: any value)
+ * when absent; a half-given group is NCF_ERR_ARG.
+ * Re-scoring (queries, items, item_bias, dim = 64, item_norm_max, c; present iff queries != NULL):
+ * the candidates of a one- or two-term split scan, whose logits are within c |q_u| max|p| of fp32;
+ * those near the K-th are recomputed in fp32 and the select runs on the recomputed logits.
+ * thr_check (may be NULL): per user, a threshold T the collect was run below (its rank-j sample
  * logit, j < K, before the margins) that is not a guaranteed bound of the K-th logit.  Every item
  * with fp32 logit >= T was collected, so the K selected are exact iff K were found and the K-th
  * re-scored logit is >= T; otherwise overflow[slot] = 2 and the caller re-runs the user from a
- * guaranteed threshold (the sample's K-th). */
-int ncf_score_select(const int32_t* user_list, int64_t n_users, const uint32_t* count,
-                     const ncf_score_cand* cand, int64_t cap, int K,
-                     float* out_score, int64_t* out_item, float* thr, uint32_t* overflow,
-                     void* stream);
-/* The two selects leaving out the items each user has already seen.  user_ids: the ids the
+ * guaranteed threshold (the sample's K-th).
+ * Exclusion (user_ids, num_users, seen_offsets, seen_items, item_ids; present iff user_ids !=
+ * NULL): leaves out the items each user has already seen.  user_ids: the ids the
  * queries were built from, indexed like them; seen_offsets [num_users + 1] / seen_items: every
  * user's seen items as a CSR over the whole user table, global item ids sorted ascending and
  * unique within a user; item_ids (may be NULL): the global id of each index position, for an
@@ -791,25 +788,16 @@ int ncf_score_select(const int32_t* user_list, int64_t n_users, const uint32_t* 
  * has no list.  Fewer than K remaining: the trailing slots are (0, -1), and with thr_check the
  * user is flagged 2; so is a user whose list overflowed with fewer than K of the cap records
  * remaining (thr is then left as it was; otherwise an overflow returns the K-th remaining logit
- * in thr, flag 1, as ncf_score_select does).  thr_check here may be any threshold the collect ran at or below: it makes
- * the result provably the top K of the unseen items (the collect's own threshold bounds the K-th
- * logit of the whole catalogue only). */
-int ncf_score_select_excl(const int32_t* user_list, int64_t n_users, const uint32_t* count,
-                          const ncf_score_cand* cand, int64_t cap, int K, float* out_score,
-                          int64_t* out_item, float* thr, uint32_t* overflow,
-                          const float* thr_check, const int64_t* user_ids, int64_t num_users,
-                          const int64_t* seen_offsets, const int32_t* seen_items,
-                          const int64_t* item_ids, void* stream);
-int ncf_score_select_rescored_excl(const int32_t* user_list, int64_t n_users,
-                                   const uint32_t* count, const ncf_score_cand* cand,
-                                   int64_t cap, int K, const float* queries, const float* items,
-                                   const float* item_bias, int64_t dim,
-                                   const uint32_t* item_norm_max, float c, float* out_score,
-                                   int64_t* out_item, float* thr, uint32_t* overflow,
-                                   const float* thr_check, const int64_t* user_ids,
-                                   int64_t num_users, const int64_t* seen_offsets,
-                                   const int32_t* seen_items, const int64_t* item_ids,
-                                   void* stream);
+ * in thr, flag 1, as without exclusion).  thr_check here may be any threshold the collect ran at
+ * or below: it makes the result provably the top K of the unseen items (the collect's own
+ * threshold bounds the K-th logit of the whole catalogue only). */
+int ncf_score_select(const int32_t* user_list, int64_t n_users, const uint32_t* count,
+                     const ncf_score_cand* cand, int64_t cap, int K, const float* queries,
+                     const float* items, const float* item_bias, int64_t dim,
+                     const uint32_t* item_norm_max, float c, float* out_score, int64_t* out_item,
+                     float* thr, uint32_t* overflow, const float* thr_check,
+                     const int64_t* user_ids, int64_t num_users, const int64_t* seen_offsets,
+                     const int32_t* seen_items, const int64_t* item_ids, void* stream);
 /* Item-sharded scoring: merge per-user lists of L = W*K (score, global item id)
  * gathered from W item shards into the top-K by (score desc, item id asc); id < 0 = empty slot
  * (an empty output slot is (0, -1)).  L, K <= 8192; item ids < 2^32 - 1. */
@@ -833,7 +821,7 @@ int ncf_score_merge(const float* cand_score, const int64_t* cand_item, int64_t n
  *   ncf_rank_pair_logits; count is zeroed by the caller; one integer atomic per row and item
  *   block of items_per_block items (a multiple of 32; 0: chosen to fill the chip).
  * ncf_rank_seen_correct: count[r] -= #{ j in seen(user_ids[r]) : beats(j) }, after the scan on
- *   the same stream; seen_offsets / seen_items: the CSR of ncf_score_select_excl (a user id
+ *   the same stream; seen_offsets / seen_items: the CSR of ncf_score_select's exclusion (a user id
  *   outside [0, num_users) has no list; a seen id outside the catalogue is skipped, err 4). */
 int ncf_rank_pair_logits(const float* queries, int64_t n_queries, const int32_t* rows,
                          const int32_t* pair_items, int64_t n_pairs, const float* items,

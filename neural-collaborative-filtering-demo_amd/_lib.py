@@ -201,12 +201,8 @@ SIGNATURES = {
     "ncf_score_collect_split": (I32, [P, P, I64, P, P, I64, I64, P, I64, P, P, I32, I64, P]),
     "ncf_score_item_norm_max": (I32, [P, I64, I64, P, P]),
     "ncf_score_margin": (I32, [P, P, I64, I64, P, F32, P, P]),
-    "ncf_score_select_rescored": (I32, [P, I64, P, P, I64, I32, P, P, P, I64, P, F32, P, P, P,
-                                        P, P, P]),
-    "ncf_score_select": (I32, [P, I64, P, P, I64, I32, P, P, P, P, P]),
-    "ncf_score_select_excl": (I32, [P, I64, P, P, I64, I32, P, P, P, P, P, P, I64, P, P, P, P]),
-    "ncf_score_select_rescored_excl": (I32, [P, I64, P, P, I64, I32, P, P, P, I64, P, F32, P, P, P,
-                                             P, P, P, I64, P, P, P, P]),
+    "ncf_score_select": (I32, [P, I64, P, P, I64, I32, P, P, P, I64, P, F32, P, P, P, P, P,
+                               P, I64, P, P, P, P]),
     "ncf_score_merge": (I32, [P, P, I64, I64, I32, P, P, P]),
     "ncf_rank_pair_logits": (I32, [P, I64, P, P, I64, P, P, I64, I64, P, P, P]),
     "ncf_rank_scan": (I32, [P, I64, P, P, I64, I64, P, P, I64, P, P]),

@@ -74,6 +74,14 @@ __device__ __forceinline__ float group_sum(float v) {
 
 __device__ __forceinline__ float wave_sum(float v) { return group_sum<64>(v); }
 
+// LDS writes of this wave visible to its other lanes, for a slice no other wave touches
+// (LDS-only fence: no global cache traffic)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 

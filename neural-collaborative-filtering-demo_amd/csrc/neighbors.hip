@@ -27,11 +27,11 @@
 // categories travel with their tiles), and the one position a query skips.
 // A NaN similarity fails the first comparison (sim >= bar) and is never kept.
 #include "ncf_common.h"
+#include "scan_tile_dev.h"   // the query half, the MFMA chain and the row map (the tiling is its own)
 #include "select_dev.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 
 constexpr int kNW = 4;      // waves per workgroup: one 32-item tile each per step
@@ -123,15 +123,10 @@ __global__ __launch_bounds__(64 * kNW) void k_nn_scan(
   float a[KH];
   {
     const bool v = i < nq;
-    const float* qp = queries + (q0 + (v ? i : 0)) * D + KH * h;
+    scan_load_half<KH>(queries + (q0 + (v ? i : 0)) * D + KH * h, a, v);
     float ss = 0.0f;
 #pragma unroll
-    for (int c = 0; c < KH / 4; ++c) {
-      const float4 x = v ? ld4(qp + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
-      a[4 * c] = x.x; a[4 * c + 1] = x.y; a[4 * c + 2] = x.z; a[4 * c + 3] = x.w;
-      ss = fmaf(x.x, x.x, ss); ss = fmaf(x.y, x.y, ss);
-      ss = fmaf(x.z, x.z, ss); ss = fmaf(x.w, x.w, ss);
-    }
+    for (int k = 0; k < KH; ++k) ss = fmaf(a[k], a[k], ss);
     ss += __shfl_xor(ss, 32, 64);   // (both halves form the same sum)
     if (normalize && ss > 0.0f) {   // a zero row stays zero; a NaN row stays NaN
       const float nrm = sqrtf(ss);
@@ -139,10 +134,7 @@ __global__ __launch_bounds__(64 * kNW) void k_nn_scan(
       for (int k = 0; k < KH; ++k) a[k] = a[k] / nrm;
     }
   }
-  // (consumed here: with their loads pending at the loop header, every iteration's first MFMA
-  // would wait for all outstanding loads, the next tile's prefetch included; see k_collect)
-#pragma unroll
-  for (int k = 0; k < KH; ++k) asm volatile("" ::"v"(a[k]));
+  scan_consume<KH>(a);
   const int64_t it0 = (int64_t)blockIdx.x * slab_items;
   const int64_t it1 = min(n_items, it0 + slab_items);
   const int64_t ntiles = it0 < it1 ? (it1 - it0 + 31) / 32 : 0;
@@ -180,14 +172,8 @@ __global__ __launch_bounds__(64 * kNW) void k_nn_scan(
     // make the compiler wait for every outstanding load, the other ring slots' included, before
     // the next slot is stored)
     fetch(t0 + (int64_t)kPD * kNW * 32, v, vc);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    const float* pb_row = ps + i * PITCH + KH * h;
-#pragma unroll
-    for (int s = 0; s < KH; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], pb_row[s], acc, 0, 0, 0);
-    // acc[r]: query row (r & 3) + 8 (r >> 2) + 4 h, item t0 + i
+    // acc[r]: query row scan_row(r, h), item t0 + i
+    const f32x16 acc = scan_chain<KH>(a, ps + i * PITCH + KH * h);
     const int64_t pos = t0 + i;
     const bool ivalid = pos < it1;
     float th[16];
@@ -205,7 +191,7 @@ __global__ __launch_bounds__(64 * kNW) void k_nn_scan(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (!((hm >> r) & 1u)) continue;
-        const int ql = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int ql = scan_row(r, h);
         if (ql >= nq) continue;
         if constexpr (CAT) {
           const int qc = qcat[ql];

@@ -5,27 +5,25 @@
 // q_r . p_j + bias_j of the factorised scorer.  A count: no candidate lists, caps, thresholds or
 // re-runs, and an integer result, so the atomics leave it deterministic.
 //
-// Every logit compared here comes from ONE arithmetic, pair_logit's: a chain of D/2
-// v_mfma_f32_32x32x2_f32 from a zero accumulator with MFMA step s at k = s + (D/2)h (h: the
-// lane half), then one fp32 add of the bias.  An f32 MFMA output element is the k-ordered fmaf
-// chain of its A row and B column, whatever its place in the 32 x 32 tile, so the held-out item's
-// logit (ncf_rank_pair_logits: 32 (row, item) pairs per wave on the tile's diagonal), the scan's
+// Every logit compared here comes from ONE arithmetic, scan_tile_dev.h's scan_chain (the one
+// score.hip's k_collect runs): D/2 v_mfma_f32_32x32x2_f32 from a zero accumulator with MFMA step
+// s at k = s + (D/2)h (h: the lane half), then one fp32 add of the bias.  An f32 MFMA output
+// element is the k-ordered fmaf chain of its A row and B column, whatever its place in the
+// 32 x 32 tile, so the held-out item's logit (ncf_rank_pair_logits: 32 (row, item) pairs per wave on the tile's diagonal), the scan's
 // logit of the same item (k_rank) and a seen item's logit (k_seen_correct, diagonal again) are the
 // same bits, and two items with bit-identical row and bias tie exactly.  The j != h guard keeps an
 // item from beating itself even if that did not hold.
 //   1. ncf_rank_pair_logits   target[r] = s of (row r, held[r]);
 //   2. ncf_rank_scan          count[r] += #{ j in the block's items : beats(j) } (k_rank: the
-//                             tiling of score.hip's k_collect with the filter made a count);
+//                             tile loop of score.hip's k_collect, scan_tiles, with a count as
+//                             its consumer);
 //   3. ncf_rank_seen_correct  count[r] -= #{ j in seen(u_r) : beats(j) }, O(seen) work, so the
 //                             scan needs no per-item lookup.
 #include "ncf_common.h"
+#include "scan_tile_dev.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kRowsPerBlock = 256;   // 8 waves x 32 queried rows
-constexpr int kItemTile = 32;
 constexpr int kBadItem = 4;          // err_flag bit: an item id outside the catalogue
 
 // beats(j) as 0 / 1 without a branch (a lower id beats at s >= s_h, a higher one at s > s_h, h
@@ -37,27 +35,20 @@ __device__ __forceinline__ int32_t beats(float s, int32_t j, float sh, int32_t h
 
 // The logit of pair i (i = lane & 31) of a wave's 32 (query row, item) pairs: lane (i, h) passes
 // its pair's row and item pointers advanced by (D/2)h.  The 32 x 32 product of the 32 rows and
-// the 32 items holds pair i's dot product on its diagonal: column i (lanes i and i + 32), row i =
-// (r & 3) + 8 (r >> 2) + 4 h, so in lane half h = (i >> 2) & 1, register (i & 3) + 4 (i >> 3).
+// the 32 items holds pair i's dot product on its diagonal: column i (lanes i and i + 32), row i,
+// so in lane half scan_diag_half(i), register scan_diag_reg(i).
 // Returns it (plus b) in that lane, `own` true there; every lane of the wave must call this.
 template <int D>
 __device__ __forceinline__ float pair_logit(const float* __restrict__ qp,
                                             const float* __restrict__ pp, float b, int i, int h,
                                             bool& own) {
   constexpr int KH = D / 2;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-  for (int v = 0; v < KH / 4; ++v) {
-    const float4 x = ld4(qp + 4 * v), y = ld4(pp + 4 * v);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, y.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, y.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, y.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, y.w, acc, 0, 0, 0);
-  }
-  own = h == ((i >> 2) & 1);
-  const int rsel = (i & 3) + 4 * (i >> 3);
+  float x[KH], y[KH];
+  scan_load_half<KH>(qp, x);
+  scan_load_half<KH>(pp, y);
+  const f32x16 acc = scan_chain<KH>(x, y);
+  own = h == scan_diag_half(i);
+  const int rsel = scan_diag_reg(i);
   float d = 0.0f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) d = r == rsel ? acc[r] : d;
@@ -88,48 +79,32 @@ __global__ __launch_bounds__(256) void k_pair_logits(
   if (own && valid) out[e] = s;
 }
 
-// ---- 2. the scan.  k_collect's tiling (score.hip): a 512-thread workgroup owns 256 queried
-// rows (8 waves x 32), q in registers (k-permuted as above), 32-item tiles of p and bias through
-// double-buffered LDS ([32][D + 1] pitch: conflict-free) behind a register prefetch; per tile a
-// wave issues D/2 MFMAs and adds beats() of its 32 x 32 logits into 16 per-lane counters (row
-// (r & 3) + 8 (r >> 2) + 4 h, item = the lane's column).  After the loop the 32 lanes of a half
-// are summed and lanes 0..15 of each half add one row's count to count[row].
+// ---- 2. the scan.  k_collect's tiling (scan_tile_dev.h scan_tiles): a 512-thread workgroup
+// owns 256 queried rows (8 waves x 32), q in registers, 32-item tiles of p and bias through the
+// shared tile loop; per tile a wave adds beats() of its 32 x 32 logits into 16 per-lane counters
+// (row scan_row(r, h), item = the lane's column).  After the loop the 32 lanes of a half are
+// summed and lanes 0..15 of each half add one row's count to count[row].
 template <int D>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(D == 64 ? 4 : 2))) void k_rank(
     const float* __restrict__ q, int64_t n_rows, const float* __restrict__ items,
     const float* __restrict__ bias, int64_t n_items, int64_t items_per_block,
     const float* __restrict__ target, const int32_t* __restrict__ held,
     int32_t* __restrict__ count) {
-  static_assert(D == 64 || D == 128, "the rank scan takes 64- or 128-deep rows");
   constexpr int KH = D / 2;      // k per lane half (MFMA step s: k = s + KH h)
-  constexpr int NV = D / 64;     // float4 per thread to stage a 32 x D tile
-  __shared__ float ps[2][kItemTile][D + 1];
-  __shared__ float bs[2][kItemTile];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int i = lane & 31, h = lane >> 5;
-  const int64_t slot0 = (int64_t)blockIdx.y * kRowsPerBlock + w * 32;
+  const int64_t slot0 = (int64_t)blockIdx.y * kScanRows + w * 32;
   const int64_t my_row = slot0 + i < n_rows ? slot0 + i : 0;
   float a[KH];
-  {
-    const float* qp = q + my_row * D + KH * h;
-#pragma unroll
-    for (int v = 0; v < KH / 4; ++v) {
-      const float4 x = ld4(qp + 4 * v);
-      a[4 * v] = x.x; a[4 * v + 1] = x.y; a[4 * v + 2] = x.z; a[4 * v + 3] = x.w;
-    }
-  }
-  // Consume the query registers here: with their loads still pending at the loop header the
-  // compiler's wait-count pass puts a vmcnt(0) in front of their first MFMA in EVERY iteration,
-  // which also drains the next tile's prefetch and exposes its HBM latency (k_collect).
-#pragma unroll
-  for (int k = 0; k < KH; ++k) asm volatile("" ::"v"(a[k]));
+  scan_load_half<KH>(q + my_row * D + KH * h, a);
+  scan_consume<KH>(a);
   // the 16 rows whose logits this lane holds: target logit, held-out id, running count.  A row
   // past n_rows never counts (+inf target, id -1) and is never written.
   float tg[16];
   int32_t hid[16], cnt[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int64_t s = slot0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int64_t s = slot0 + scan_row(r, h);
     const bool v = s < n_rows;
     tg[r] = v ? target[s] : INFINITY;
     hid[r] = v ? held[s] : -1;
@@ -137,48 +112,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(D == 64 ? 4
   }
   const int64_t it0 = (int64_t)blockIdx.x * items_per_block;
   const int64_t it1 = min(n_items, it0 + items_per_block);
-  // staging: 512 threads x NV float4 = one 32 x D tile
-  const int sj = tid >> 4, sk = (tid & 15) * 4;
-  float4 pv[NV];
-  float pb = 0.0f;
-  auto fetch = [&](int64_t t0) {
-    const int64_t item = t0 + sj;
-    const int64_t src = item < it1 ? item : it0;  // clamped, unconditional
+  scan_tiles<D>(
+      a, items, bias, it0, it1, [] {},
+      [&](const f32x16& acc, float b, int64_t item64, bool inside) {
+        const int32_t item = (int32_t)item64;
+        const int32_t ivalid = inside ? 1 : 0;
 #pragma unroll
-    for (int c = 0; c < NV; ++c) pv[c] = ld4(items + src * D + sk + 64 * c);
-    pb = bias[src];
-  };
-  // the load of tile t + 1 is issued while tile t is multiplied
-  if (it0 < it1) fetch(it0);
-  int buf = 0;
-  for (int64_t t0 = it0; t0 < it1; t0 += kItemTile) {
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      float* dst = &ps[buf][sj][sk + 64 * c];
-      dst[0] = pv[c].x; dst[1] = pv[c].y; dst[2] = pv[c].z; dst[3] = pv[c].w;
-    }
-    if ((tid & 15) == 0) bs[buf][sj] = pb;
-    // (one barrier per tile: a wave writes buffer `buf` again two tiles on, after the barrier
-    // of the tile between, which every wave passes only when it has read this one)
-    __syncthreads();
-    if (t0 + kItemTile < it1) fetch(t0 + kItemTile);
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    const float* pb_row = &ps[buf][i][KH * h];
-#pragma unroll
-    for (int s = 0; s < KH; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], pb_row[s], acc, 0, 0, 0);
-    const int64_t item64 = t0 + i;
-    const int32_t item = (int32_t)item64;
-    const float b = bs[buf][i];
-    const int32_t ivalid = item64 < it1 ? 1 : 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cnt[r] += beats(acc[r] + b, item, tg[r], hid[r]) & ivalid;
-    buf ^= 1;
-  }
+        for (int r = 0; r < 16; ++r) cnt[r] += beats(acc[r] + b, item, tg[r], hid[r]) & ivalid;
+      });
   // sum over the 32 lanes of a half (xor offsets < 32 stay inside it); lane i < 16 of half h
-  // then owns row (i & 3) + 8 (i >> 2) + 4 h
+  // then owns row scan_row(i, h)
   int32_t mine = 0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -188,7 +131,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(D == 64 ? 4
     mine = i == r ? c : mine;
   }
   if (i < 16) {
-    const int64_t s = slot0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+    const int64_t s = slot0 + scan_row(i, h);
     if (s < n_rows && mine != 0) atomicAdd(&count[s], mine);
   }
 }
@@ -227,17 +170,6 @@ __global__ __launch_bounds__(256) void k_seen_correct(
     total += __popcll(__ballot(own && valid && beats(s, (int32_t)item, sh, hd)));
   }
   if (lane == 0 && total != 0) count[row] -= total;
-}
-
-int64_t rank_items_per_block(int64_t n_rows, int64_t n_items) {
-  // as ncf_score_collect: enough workgroups to fill the chip (>= ~2 per CU), >= 8 tiles each
-  const int64_t rb = (n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
-  int64_t splits = (1024 + rb - 1) / rb;
-  const int64_t max_splits = (n_items + 8 * kItemTile - 1) / (8 * kItemTile);
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  const int64_t per = (n_items + splits - 1) / splits;
-  return (per + kItemTile - 1) / kItemTile * kItemTile;
 }
 
 }  // namespace
@@ -280,9 +212,9 @@ extern "C" int ncf_rank_scan(const float* queries, int64_t n_rows, const float* 
                 "ncf_rank_scan: null pointer");
   NCF_CHECK_ARG((((uintptr_t)queries | (uintptr_t)items) & 15) == 0,
                 "ncf_rank_scan: rows must be 16-B aligned");
-  const int64_t per = items_per_block ? items_per_block : rank_items_per_block(n_rows, n_items);
+  const int64_t per = items_per_block ? items_per_block : scan_items_per_block(n_rows, n_items);
   const int64_t splits = (n_items + per - 1) / per;
-  const int64_t rb = (n_rows + kRowsPerBlock - 1) / kRowsPerBlock;
+  const int64_t rb = (n_rows + kScanRows - 1) / kScanRows;
   NCF_CHECK_ARG(rb < 65536, "ncf_rank_scan: too many rows per call (max %d)", 65535 * 256);
   const dim3 grid((unsigned)splits, (unsigned)rb);
   if (dim == 64)

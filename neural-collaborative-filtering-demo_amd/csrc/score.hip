@@ -21,24 +21,23 @@
 //                             order gives the same result.  With one or two terms the scan's
 //                             logits are bounds (within E_u = c |q_u| max|p|, c = 8e-3 / 1e-4):
 //                             ncf_score_margin lowers the thresholds by E_u first;
-//   4. ncf_score_select(_rescored)  per user, radix select of the K-th candidate key in LDS, the K
+//   4. ncf_score_select       per user, radix select of the K-th candidate key in LDS, the K
 //                             winners sorted (after 1/2-term scans: the candidates within 2 E_u of
 //                             the scan's K-th re-scored in fp32 first); when a user's list
 //                             overflowed, the K-th best candidate seen is a higher valid threshold
 //                             and the host re-runs 3-4 for those users.  With a rank-j threshold
 //                             (j < K, a smaller sample: thr_check) it also checks that the K chosen
 //                             are provably the top K, and flags the user for a re-run if not.
-//                             ncf_score_select*_excl: the same without the candidates in the user's
-//                             list of seen items (k_select<.., EX>), always with thr_check.
-// Tilings: see k_collect (fp32) and k_collect3 (split bf16) below.
+//                             With its exclusion arguments: the same without the candidates in the
+//                             user's list of seen items (k_select<.., EX>), always with thr_check.
+// Tilings: see k_collect (fp32; scan_tile_dev.h) and k_collect3 (split bf16) below.
 #include "ncf_common.h"
-#include "select_dev.h"   // fkey / fkey_inv, wave_lds_sync, bitonic_desc
+#include "scan_tile_dev.h"   // the fp32 MFMA scan tile: k_collect
+#include "select_dev.h"      // fkey / fkey_inv, bitonic_desc
 #include <algorithm>
 #include <type_traits>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- 1. queries: q = w0 * LN(U_mf[id]) (.) w_mf; L = D/4 lanes per row.  The rows are QD =
 // max(64, D) floats wide: a D < 64 row is zero-padded (the item index pads its rows the same way,
@@ -365,18 +364,12 @@ __global__ __launch_bounds__(256) void k_score_margin(const float* __restrict__ 
 
 // ---- 3. MFMA scan + threshold filter
 // fp32 tiling (k_collect): a 512-thread workgroup owns 256 users (8 waves x 32), keeps each
-// wave's q rows in registers (k-permuted: MFMA step s uses k = s + (D/2)h), and streams 32-item
-// tiles of p through double-buffered LDS ([32][D+1] pitch: conflict-free); per tile a wave issues
-// D/2 v_mfma_f32_32x32x2_f32 and filters its 32x32 logits against 16 per-lane thresholds (D = 64,
-// or 128: the C4 model's width, two k chunks per tile).  Hits are
+// wave's q rows in registers and streams 32-item tiles of p through the shared tile loop
+// (scan_tile_dev.h scan_tiles: double-buffered LDS, D/2 v_mfma_f32_32x32x2_f32 per wave and
+// tile); per tile a wave filters its 32x32 logits against 16 per-lane thresholds (D = 64, or
+// 128: the C4 model's width, two k chunks per tile).  Hits are
 // staged in LDS (one LDS atomic per wave and tile) and flushed to the global per-user lists in
 // parallel bursts (a global atomic per hit made the wave wait thousands of cycles per tile).
-constexpr int kUsersPerBlock = 256;  // 8 waves x 32
-constexpr int kItemTile = 32;
-#ifndef NCF_SCORE_PD
-#define NCF_SCORE_PD 1
-#endif
-constexpr int kPD = NCF_SCORE_PD;     // item tiles in flight (register ring)
 constexpr int kCandBuf = 2048;        // LDS-staged candidates per workgroup (flushed at half)
 
 template <int D>
@@ -385,11 +378,7 @@ __global__ __launch_bounds__(512) void k_collect(
     const float* __restrict__ items, const float* __restrict__ bias, int64_t n_items,
     int64_t items_per_block, const float* __restrict__ thr, int64_t cap,
     uint32_t* __restrict__ count, ncf_score_cand* __restrict__ cand) {
-  static_assert(D == 64 || D == 128, "the fp32 scan takes 64- or 128-deep rows");
   constexpr int KH = D / 2;      // k per lane half (MFMA step s: k = s + KH h)
-  constexpr int NV = D / 64;     // float4 per thread to stage a 32 x D tile
-  __shared__ float ps[2][kItemTile][D + 1];
-  __shared__ float bs[2][kItemTile];
   // Candidates are staged in LDS (an LDS atomic returns in ~100 cycles; a global one in
   // thousands, and a wave waits for it in the filter of nearly every tile) and flushed to the
   // per-user global lists in parallel bursts.  The lists are sets (select sorts them), so the
@@ -401,55 +390,25 @@ __global__ __launch_bounds__(512) void k_collect(
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int i = lane & 31, h = lane >> 5;
   // this wave's 32 users (slot = index into the user list)
-  const int64_t slot0 = (int64_t)blockIdx.y * kUsersPerBlock + w * 32;
+  const int64_t slot0 = (int64_t)blockIdx.y * kScanRows + w * 32;
   const int64_t my_slot = slot0 + i;
   const bool uvalid = my_slot < n_users;
   const int64_t my_user = uvalid ? (user_list ? user_list[my_slot] : my_slot) : 0;
   float a[KH];
-  {
-    const float* qp = q + my_user * D + KH * h;
-#pragma unroll
-    for (int v = 0; v < KH / 4; ++v) {
-      const float4 x = ld4(qp + 4 * v);
-      a[4 * v] = x.x; a[4 * v + 1] = x.y; a[4 * v + 2] = x.z; a[4 * v + 3] = x.w;
-    }
-  }
-  // Consume the query registers here: with their loads still pending at the loop header the
-  // compiler's wait-count pass puts a vmcnt(0) in front of their first MFMA in EVERY
-  // iteration, which also drains the next tile's prefetch and exposes its HBM latency (measured:
-  // the matrix cores idle half the time).
-#pragma unroll
-  for (int k = 0; k < KH; ++k) asm volatile("" ::"v"(a[k]));
-  // thresholds of the 16 users whose logits this lane holds: row (r&3) + 8(r>>2) + 4h
+  scan_load_half<KH>(q + my_user * D + KH * h, a);
+  scan_consume<KH>(a);
+  // thresholds of the 16 users whose logits this lane holds
   float th[16];
   int64_t urow[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int64_t s = slot0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int64_t s = slot0 + scan_row(r, h);
     const bool v = s < n_users;
     urow[r] = v ? (user_list ? user_list[s] : s) : -1;
     th[r] = v ? thr[urow[r]] : INFINITY;
   }
   const int64_t it0 = (int64_t)blockIdx.x * items_per_block;
   const int64_t it1 = min(n_items, it0 + items_per_block);
-  // staging: 512 threads x NV float4 = one 32 x D tile
-  const int sj = tid >> 4, sk = (tid & 15) * 4;
-  auto fetch = [&](int64_t t0, float4 (&v)[NV], float& bv) {
-    const int64_t item = t0 + sj;
-    const int64_t src = item < it1 ? item : it0;  // clamped, unconditional
-#pragma unroll
-    for (int c = 0; c < NV; ++c) v[c] = ld4(items + src * D + sk + 64 * c);
-    bv = bias[src];
-  };
-  // register ring of kPD staged tiles: the load of tile t + kPD is issued while tile t is
-  // multiplied, so a tile's HBM latency hides behind kPD tiles of MFMAs (one tile alone,
-  // ~2K cycles per wave, is shorter than a loaded HBM miss)
-  float4 pv[kPD][NV];
-  float pb[kPD];
-#pragma unroll
-  for (int d = 0; d < kPD; ++d)
-    if (it0 + d * kItemTile < it1) fetch(it0 + d * kItemTile, pv[d], pb[d]);
-  int buf = 0, slot = 0;
   auto flush = [&](uint32_t nstaged) {
     const uint32_t m = nstaged < (uint32_t)kCandBuf ? nstaged : (uint32_t)kCandBuf;
     for (uint32_t e = threadIdx.x; e < m; e += blockDim.x) {
@@ -458,82 +417,50 @@ __global__ __launch_bounds__(512) void k_collect(
       if (pos < cap) cand[(int64_t)u * cap + pos] = ncf_score_cand{cl[e], ci[e]};
     }
   };
-  for (int64_t t0 = it0; t0 < it1; t0 += kItemTile) {
-    float4 cur[NV];
-    float cb = pb[0];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) cur[c] = pv[0][c];
-#pragma unroll
-    for (int d = 1; d < kPD; ++d)   // (static slot selection: the ring rotates by one)
-      if (slot == d) {
-#pragma unroll
-        for (int c = 0; c < NV; ++c) cur[c] = pv[d][c];
-        cb = pb[d];
-      }
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-      float* dst = &ps[buf][sj][sk + 64 * c];
-      dst[0] = cur[c].x; dst[1] = cur[c].y; dst[2] = cur[c].z; dst[3] = cur[c].w;
-    }
-    if ((tid & 15) == 0) bs[buf][sj] = cb;
-    __syncthreads();
-    {
-      const uint32_t staged = ccount;     // uniform: read after the barrier
-      if (staged >= (uint32_t)kCandBuf / 2) {
-        flush(staged);
-        __syncthreads();
-        if (threadIdx.x == 0) ccount = 0;
-        __syncthreads();
-      }
-    }
-    if (t0 + kPD * kItemTile < it1) {
-#pragma unroll
-      for (int d = 0; d < kPD; ++d)
-        if (slot == d) fetch(t0 + kPD * kItemTile, pv[d], pb[d]);
-    }
-    slot = slot + 1 == kPD ? 0 : slot + 1;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    const float* pb_row = &ps[buf][i][KH * h];
-#pragma unroll
-    for (int s = 0; s < KH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], pb_row[s], acc, 0, 0, 0);
-    const int64_t item = t0 + i;
-    const float b = bs[buf][i];
-    const bool ivalid = item < it1;
-    uint32_t hm = 0;   // this lane's hits of the tile (bit r: user row r)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) hm |= (ivalid && acc[r] + b >= th[r]) ? (1u << r) : 0u;
-    if (__ballot(hm != 0)) {   // wave-uniform; hits are rare (~1 per wave and tile)
-      // one LDS atomic per wave: exclusive prefix of the lanes' hit counts
-      const uint32_t nh = (uint32_t)__popc(hm);
-      uint32_t incl = nh;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t x = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += x;
-      }
-      uint32_t base = 0;
-      if (lane == 63) base = atomicAdd(&ccount, incl);
-      base = __shfl(base, 63, 64) + incl - nh;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (hm & (1u << r)) {
-          const float lg = acc[r] + b;
-          if (base < (uint32_t)kCandBuf) {
-            cl[base] = lg;
-            ci[base] = (int32_t)item;
-            cu[base] = (int32_t)urow[r];
-          } else {   // staging full within this tile: straight to the global list
-            const uint32_t pos = atomicAdd(&count[urow[r]], 1u);
-            if (pos < cap) cand[urow[r] * cap + pos] = ncf_score_cand{lg, (int32_t)item};
-          }
-          ++base;
+  scan_tiles<D>(
+      a, items, bias, it0, it1,
+      [&] {
+        const uint32_t staged = ccount;     // uniform: read after the barrier
+        if (staged >= (uint32_t)kCandBuf / 2) {
+          flush(staged);
+          __syncthreads();
+          if (threadIdx.x == 0) ccount = 0;
+          __syncthreads();
         }
-      }
-    }
-    buf ^= 1;
-  }
+      },
+      [&](const f32x16& acc, float b, int64_t item, bool ivalid) {
+        uint32_t hm = 0;   // this lane's hits of the tile (bit r: user row r)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hm |= (ivalid && acc[r] + b >= th[r]) ? (1u << r) : 0u;
+        if (__ballot(hm != 0)) {   // wave-uniform; hits are rare (~1 per wave and tile)
+          // one LDS atomic per wave: exclusive prefix of the lanes' hit counts
+          const uint32_t nh = (uint32_t)__popc(hm);
+          uint32_t incl = nh;
+#pragma unroll
+          for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t x = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += x;
+          }
+          uint32_t base = 0;
+          if (lane == 63) base = atomicAdd(&ccount, incl);
+          base = __shfl(base, 63, 64) + incl - nh;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            if (hm & (1u << r)) {
+              const float lg = acc[r] + b;
+              if (base < (uint32_t)kCandBuf) {
+                cl[base] = lg;
+                ci[base] = (int32_t)item;
+                cu[base] = (int32_t)urow[r];
+              } else {   // staging full within this tile: straight to the global list
+                const uint32_t pos = atomicAdd(&count[urow[r]], 1u);
+                if (pos < cap) cand[urow[r] * cap + pos] = ncf_score_cand{lg, (int32_t)item};
+              }
+              ++base;
+            }
+          }
+        }
+      });
   __syncthreads();
   flush(ccount);
 }
@@ -856,7 +783,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
             (uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
         wl[at] = acc[r] + b;
         wi[at] = item;
-        wu[at] = (uint16_t)(32 * ub + (r & 3) + 8 * (r >> 2) + 4 * h);   // local user slot
+        wu[at] = (uint16_t)(32 * ub + scan_row(r, h));   // local user slot
       }
       staged += nh;
     }
@@ -1069,7 +996,7 @@ __global__ __launch_bounds__(256) void k_sample16(const float* __restrict__ q, i
         const float b = bs[32 * jt + i];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int64_t u = u0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int64_t u = u0 + scan_row(r, h);
           if (u < n_users)
             out[u * S + j] = __builtin_bit_cast(_Float16, __ocml_cvtrtn_f16_f32(acc[r] + b));
         }
@@ -1081,7 +1008,7 @@ __global__ __launch_bounds__(256) void k_sample16(const float* __restrict__ q, i
         float v = j < S ? acc[r] + b : -INFINITY;
 #pragma unroll
         for (int o = 1; o < G; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-        const int64_t u = u0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t u = u0 + scan_row(r, h);
         if (i % G == 0 && j < S && u < n_users)
           out[u * Sg + j / G] = __builtin_bit_cast(_Float16, __ocml_cvtrtn_f16_f32(v));
       }
@@ -1612,15 +1539,9 @@ extern "C" int ncf_score_collect(const float* queries, const int32_t* user_list,
   NCF_CHECK_ARG(n_users >= 0 && n_items >= 0 && n_items < (1ll << 31) && cap >= 1,
                 "ncf_score_collect: bad size");
   if (n_users == 0 || n_items == 0) return NCF_OK;
-  // item split: enough workgroups to fill the chip (>= ~2 per CU) with >= 8 tiles each
-  const int64_t ub = (n_users + kUsersPerBlock - 1) / kUsersPerBlock;
-  int64_t splits = (1024 + ub - 1) / ub;
-  const int64_t max_splits = (n_items + 8 * kItemTile - 1) / (8 * kItemTile);
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  int64_t per = (n_items + splits - 1) / splits;
-  per = (per + kItemTile - 1) / kItemTile * kItemTile;
-  splits = (n_items + per - 1) / per;
+  const int64_t ub = (n_users + kScanRows - 1) / kScanRows;
+  const int64_t per = scan_items_per_block(n_users, n_items);
+  const int64_t splits = (n_items + per - 1) / per;
   NCF_CHECK_ARG(ub < 65536, "ncf_score_collect: too many users per call (max %d)", 65535 * 256);
   if (dim == 64)
     hipLaunchKernelGGL(k_collect<64>, dim3((unsigned)splits, (unsigned)ub), dim3(512), 0,
@@ -1757,7 +1678,7 @@ extern "C" int ncf_score_collect_split(const float* queries, const int32_t* user
   return NCF_OK;
 }
 
-// launch of k_select<RS, EX> (the arguments checked by the entry points below)
+// launch of k_select<RS, EX> (the arguments checked by ncf_score_select)
 template <bool RS, bool EX>
 static void select_launch(const int32_t* user_list, int64_t n_users, const uint32_t* count,
                           const ncf_score_cand* cand, int64_t cap, int K, const float* queries,
@@ -1783,86 +1704,47 @@ static void select_launch(const int32_t* user_list, int64_t n_users, const uint3
                      thr_check, user_ids, num_users, seen_offsets, seen_items, item_ids);
 }
 
+// The one entry of k_select<RS, EX>, with two optional argument groups, each all-NULL when
+// absent.  Re-scoring (queries != NULL; the one- and two-term split scans' candidates): every
+// candidate near the K-th has its logit recomputed in fp32 from queries [.., 64] and items
+// [n_items, 64] + item_bias.  Exclusion (user_ids != NULL): the candidates in the user's seen
+// list are dropped first; user_ids as the queries were built from (indexed like them), the
+// users' lists as a CSR over the whole user table, item_ids the index's position -> global id
+// map (NULL: the positions are the ids).
 extern "C" int ncf_score_select(const int32_t* user_list, int64_t n_users, const uint32_t* count,
-                                const ncf_score_cand* cand, int64_t cap,
-                                int K, float* out_score, int64_t* out_item, float* thr,
-                                uint32_t* overflow, void* stream) {
+                                const ncf_score_cand* cand, int64_t cap, int K,
+                                const float* queries, const float* items, const float* item_bias,
+                                int64_t dim, const uint32_t* item_norm_max, float c,
+                                float* out_score, int64_t* out_item, float* thr,
+                                uint32_t* overflow, const float* thr_check,
+                                const int64_t* user_ids, int64_t num_users,
+                                const int64_t* seen_offsets, const int32_t* seen_items,
+                                const int64_t* item_ids, void* stream) {
+  const bool rs = queries != nullptr, ex = user_ids != nullptr;
+  if (rs)
+    NCF_CHECK_ARG(dim == 64 && items && item_bias && item_norm_max,
+                  "ncf_score_select: re-scoring: dim must be 64, rows non-null");
+  else
+    NCF_CHECK_ARG(!items && !item_bias && !item_norm_max,
+                  "ncf_score_select: re-scoring arguments without queries");
   NCF_CHECK_ARG(n_users >= 0 && K >= 1 && cap >= K && cap <= kSelectMax,
                 "ncf_score_select: need 1 <= K <= cap <= %d", kSelectMax);
+  if (ex)
+    NCF_CHECK_ARG(seen_offsets && num_users >= 0,
+                  "ncf_score_select: exclusion: user_ids and seen_offsets must be non-null");
+  else
+    NCF_CHECK_ARG(!seen_offsets && !seen_items && !item_ids,
+                  "ncf_score_select: exclusion arguments without user_ids");
   if (n_users == 0) return NCF_OK;
-  select_launch<false, false>(user_list, n_users, count, cand, cap, K, nullptr, nullptr, nullptr,
-                              nullptr, 0.0f, out_score, out_item, thr, overflow, nullptr, nullptr,
-                              0, nullptr, nullptr, nullptr, stream);
+#define NCF_SELECT(RS, EX)                                                                       \
+  select_launch<RS, EX>(user_list, n_users, count, cand, cap, K, queries, items, item_bias,      \
+                        item_norm_max, c, out_score, out_item, thr, overflow, thr_check,         \
+                        user_ids, num_users, seen_offsets, seen_items, item_ids, stream)
+  if (rs && ex) NCF_SELECT(true, true);
+  else if (rs) NCF_SELECT(true, false);
+  else if (ex) NCF_SELECT(false, true);
+  else NCF_SELECT(false, false);
+#undef NCF_SELECT
   NCF_CHECK_LAUNCH("ncf_score_select");
-  return NCF_OK;
-}
-
-// ncf_score_select with every candidate's logit recomputed in fp32 from queries [.., 64] and
-// items [n_items, 64] + item_bias (the two-term split scan's candidates)
-extern "C" int ncf_score_select_rescored(const int32_t* user_list, int64_t n_users,
-                                         const uint32_t* count, const ncf_score_cand* cand,
-                                         int64_t cap, int K,
-                                         const float* queries, const float* items,
-                                         const float* item_bias, int64_t dim,
-                                         const uint32_t* item_norm_max, float c,
-                                         float* out_score, int64_t* out_item, float* thr,
-                                         uint32_t* overflow, const float* thr_check,
-                                         void* stream) {
-  NCF_CHECK_ARG(dim == 64 && queries && items && item_bias && item_norm_max,
-                "ncf_score_select_rescored: dim must be 64, rows non-null");
-  NCF_CHECK_ARG(n_users >= 0 && K >= 1 && cap >= K && cap <= kSelectMax,
-                "ncf_score_select_rescored: need 1 <= K <= cap <= %d", kSelectMax);
-  if (n_users == 0) return NCF_OK;
-  select_launch<true, false>(user_list, n_users, count, cand, cap, K, queries, items, item_bias,
-                             item_norm_max, c, out_score, out_item, thr, overflow, thr_check,
-                             nullptr, 0, nullptr, nullptr, nullptr, stream);
-  NCF_CHECK_LAUNCH("ncf_score_select_rescored");
-  return NCF_OK;
-}
-
-// The two selects leaving out the items each user has seen (k_select<.., true>): user_ids as
-// the queries were built from (indexed like them), the users' lists as a CSR over the whole user
-// table, item_ids the index's position -> global id map (NULL: the positions are the ids).
-extern "C" int ncf_score_select_excl(const int32_t* user_list, int64_t n_users,
-                                     const uint32_t* count, const ncf_score_cand* cand,
-                                     int64_t cap, int K, float* out_score, int64_t* out_item,
-                                     float* thr, uint32_t* overflow, const float* thr_check,
-                                     const int64_t* user_ids, int64_t num_users,
-                                     const int64_t* seen_offsets, const int32_t* seen_items,
-                                     const int64_t* item_ids, void* stream) {
-  NCF_CHECK_ARG(n_users >= 0 && K >= 1 && cap >= K && cap <= kSelectMax,
-                "ncf_score_select_excl: need 1 <= K <= cap <= %d", kSelectMax);
-  NCF_CHECK_ARG(user_ids && seen_offsets && num_users >= 0,
-                "ncf_score_select_excl: user_ids and seen_offsets must be non-null");
-  if (n_users == 0) return NCF_OK;
-  select_launch<false, true>(user_list, n_users, count, cand, cap, K, nullptr, nullptr, nullptr,
-                             nullptr, 0.0f, out_score, out_item, thr, overflow, thr_check,
-                             user_ids, num_users, seen_offsets, seen_items, item_ids, stream);
-  NCF_CHECK_LAUNCH("ncf_score_select_excl");
-  return NCF_OK;
-}
-
-extern "C" int ncf_score_select_rescored_excl(const int32_t* user_list, int64_t n_users,
-                                              const uint32_t* count, const ncf_score_cand* cand,
-                                              int64_t cap, int K, const float* queries,
-                                              const float* items, const float* item_bias,
-                                              int64_t dim, const uint32_t* item_norm_max, float c,
-                                              float* out_score, int64_t* out_item, float* thr,
-                                              uint32_t* overflow, const float* thr_check,
-                                              const int64_t* user_ids, int64_t num_users,
-                                              const int64_t* seen_offsets,
-                                              const int32_t* seen_items, const int64_t* item_ids,
-                                              void* stream) {
-  NCF_CHECK_ARG(dim == 64 && queries && items && item_bias && item_norm_max,
-                "ncf_score_select_rescored_excl: dim must be 64, rows non-null");
-  NCF_CHECK_ARG(n_users >= 0 && K >= 1 && cap >= K && cap <= kSelectMax,
-                "ncf_score_select_rescored_excl: need 1 <= K <= cap <= %d", kSelectMax);
-  NCF_CHECK_ARG(user_ids && seen_offsets && num_users >= 0,
-                "ncf_score_select_rescored_excl: user_ids and seen_offsets must be non-null");
-  if (n_users == 0) return NCF_OK;
-  select_launch<true, true>(user_list, n_users, count, cand, cap, K, queries, items, item_bias,
-                            item_norm_max, c, out_score, out_item, thr, overflow, thr_check,
-                            user_ids, num_users, seen_offsets, seen_items, item_ids, stream);
-  NCF_CHECK_LAUNCH("ncf_score_select_rescored_excl");
   return NCF_OK;
 }

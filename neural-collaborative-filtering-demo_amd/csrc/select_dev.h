@@ -11,13 +11,6 @@ __device__ __forceinline__ float fkey_inv(uint32_t k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-// LDS writes of this wave visible to its other lanes (LDS-only fence: no global cache traffic)
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
-
 // in-LDS bitonic sort of n2 (a power of two) keys, descending; the whole block participates
 __device__ __forceinline__ void bitonic_desc(unsigned long long* keys, int n2) {
   for (int size = 2; size <= n2; size <<= 1) {

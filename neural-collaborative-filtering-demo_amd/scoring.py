@@ -244,6 +244,48 @@ def _param_version(model):
     return (model._engine.updates,) + tuple(p._version for p in model.parameters())
 
 
+def _resolve_index(model, index, projection, caller: str, items=None) -> "ItemIndex":
+    """The index a call scores over: ``index`` when it is valid for the model's parameters, a
+    rebuilt one over the same items and projection when they changed since, a new one when none
+    was given (``items``: a function returning the ids a new or rebuilt index covers; default
+    the whole catalogue, or the stale index's own).  A ``projection`` beside an index must be the
+    index's own."""
+    if index is None:
+        return ItemIndex(model, items=items and items(), projection=projection)
+    if projection is not None and not index.owns_projection(projection):
+        raise ValueError(f"{caller}: index was built with another projection; pass the "
+                         "projection to ItemIndex and leave it out here")
+    if not index.valid_for(model):   # parameters changed since the index was built
+        index = ItemIndex(model, items=items() if items else index.ids,
+                          projection=index.projection)
+    return index
+
+
+def _queries(model, uid, n, q, err, st, hours=None, scale=None):
+    """The query rows of ``uid[:n]`` into ``q`` on stream ``st`` (ncf_score_queries; with
+    ``hours``: ncf_score_queries_hour, row r times ``scale[hours[r]]``).  The kernel ORs 1 into
+    ``err`` for a user id, 2 for an hour out of range."""
+    table = model.mf_embedding_collection.embedding_bags["user_id"].weight
+    rows = (ptr(table), model.num_users, model.mf_embedding_dim, ptr(model.mf_norm.weight),
+            ptr(model.mf_norm.bias), LN_EPS, ptr(model.mf_output.weight),
+            ptr(model.final[0].weight))
+    if hours is None:
+        _lib.call("ncf_score_queries", ptr(uid), n, *rows, ptr(q), ptr(err), st)
+    else:
+        _lib.call("ncf_score_queries_hour", ptr(uid), ptr(hours), n, *rows, ptr(scale), ptr(q),
+                  ptr(err), st)
+
+
+def _raise_flags(flags: int, caller: str):
+    """The kernels' error word (1: user id, 2: hour, 4: item id out of range) as an IndexError."""
+    if flags & 1:
+        raise IndexError(f"{caller}: user id out of range of the embedding table")
+    if flags & 2:
+        raise IndexError(f"{caller}: hour outside [0, 24)")
+    if flags & 4:
+        raise IndexError(f"{caller}: item id out of range of the catalogue")
+
+
 class SeenItems:
     """Every user's already-seen items, as a CSR over the whole user table: ``offsets`` int64
     ``[num_users + 1]``, ``items`` int32 global item ids, sorted ascending and unique within a
@@ -419,27 +461,17 @@ SAMPLE_GROUP = 8
 
 def _select(idx, rows, n, run, k, out_s, out_i, overflow, st, terms=None, check=None,
             exclude=None):
-    """ncf_score_select(_rescored) of n users' candidate lists (fp32 re-scoring after a one- or
-    two-term scan; ``terms`` as the scan's; ``check``: the rank-j thresholds to verify the
+    """ncf_score_select of n users' candidate lists (with its re-scoring group after a one- or
+    two-term scan, fp32; ``terms`` as the scan's; ``check``: the rank-j thresholds to verify the
     selection against, flag 2 where it is not provably the top k; ``exclude``: the users' seen
-    items, looked up by ``run.uid`` and dropped from the lists first, ncf_score_select*_excl)."""
-    if exclude is not None:
-        seen = (ptr(run.uid), exclude.num_users, ptr(exclude.offsets), ptr(exclude.items),
-                ptr(idx.ids))
-        if idx.pmax is not None:
-            _lib.call("ncf_score_select_rescored_excl", rows, n, ptr(run.count), ptr(run.cand),
-                      run.cap, k, ptr(run.q), ptr(idx.p), ptr(idx.bias), idx.p.shape[1],
-                      ptr(idx.pmax), MARGIN_C[terms or _terms(idx)], out_s, out_i, ptr(run.thr),
-                      overflow, check, *seen, st)
-        else:
-            _lib.call("ncf_score_select_excl", rows, n, ptr(run.count), ptr(run.cand), run.cap, k,
-                      out_s, out_i, ptr(run.thr), overflow, check, *seen, st)
-    elif idx.pmax is not None:
-        _lib.call("ncf_score_select_rescored", rows, n, ptr(run.count), ptr(run.cand), run.cap, k, ptr(run.q), ptr(idx.p), ptr(idx.bias),
-                  idx.p.shape[1], ptr(idx.pmax), MARGIN_C[terms or _terms(idx)], out_s, out_i,
-                  ptr(run.thr), overflow, check, st)
-    else:
-        _lib.call("ncf_score_select", rows, n, ptr(run.count), ptr(run.cand), run.cap, k, out_s, out_i, ptr(run.thr), overflow, st)
+    items, looked up by ``run.uid`` and dropped from the lists first, its exclusion group)."""
+    rescore = (None, None, None, 0, None, 0.0) if idx.pmax is None else \
+        (ptr(run.q), ptr(idx.p), ptr(idx.bias), idx.p.shape[1], ptr(idx.pmax),
+         MARGIN_C[terms or _terms(idx)])
+    seen = (None, 0, None, None, None) if exclude is None else \
+        (ptr(run.uid), exclude.num_users, ptr(exclude.offsets), ptr(exclude.items), ptr(idx.ids))
+    _lib.call("ncf_score_select", rows, n, ptr(run.count), ptr(run.cand), run.cap, k, *rescore,
+              out_s, out_i, ptr(run.thr), overflow, check, *seen, st)
 
 
 # Rank-j thresholds (the fp16 sample path, k > RANK_J): the threshold is the sample's j-th
@@ -535,19 +567,9 @@ class _TopKRun:
         idx, n, k, cap = self.index, self.n, self.k, self.cap
         p, bias = idx.p, idx.bias
         I, D = p.shape
-        table = model.mf_embedding_collection.embedding_bags["user_id"].weight
-        if self.hours is not None:   # q_u (.) s_h, h = self.hours[u's row]
-            _lib.call("ncf_score_queries_hour", ptr(self.uid), ptr(self.hours), n, ptr(table),
-                      model.num_users, model.mf_embedding_dim,
-                      ptr(model.mf_norm.weight), ptr(model.mf_norm.bias), LN_EPS,
-                      ptr(model.mf_output.weight), ptr(model.final[0].weight), ptr(idx.scale),
-                      ptr(self.q), ptr(self.err), st)
-        else:
-            _lib.call("ncf_score_queries", ptr(self.uid), n, ptr(table), model.num_users,
-                      model.mf_embedding_dim,
-                      ptr(model.mf_norm.weight), ptr(model.mf_norm.bias), LN_EPS,
-                      ptr(model.mf_output.weight), ptr(model.final[0].weight), ptr(self.q),
-                      ptr(self.err), st)
+        # (an index at an hour: q_u (.) s_h, h = self.hours[u's row])
+        _queries(model, self.uid, n, self.q, self.err, st, self.hours,
+                 idx.scale if self.hours is not None else None)
         if self.s16:
             _lib.call("ncf_score_sample_split16", ptr(self.q), n, ptr(idx.p3), I, D, self.stride,
                       ptr(self.sbias), self.S, self.G, ptr(self.sample), st)
@@ -765,11 +787,7 @@ def _topk_eager(model, uid, k, idx, cap, exclude, hours=None):
             run.hours.fill_(hours)
     run.launch(model, st)
     run.redo_overflow(st)
-    err = int(run.err.item())
-    if err & 1:
-        raise IndexError("score_topk: user id out of range of the embedding table")
-    if err & 2:
-        raise IndexError("score_topk: hour outside [0, 24)")
+    _raise_flags(int(run.err.item()), "score_topk")
     return run.result()
 
 
@@ -788,14 +806,7 @@ def score_topk(model, user_ids: torch.Tensor, k: int = 10, index: Optional[ItemI
     or ``(weight, bias)`` for the index this call builds (an ``index`` brings its own)."""
     _check_exclude(exclude, model.num_users, model.num_products)
     hour = _check_hour(hour, user_ids.numel())
-    if index is None:
-        index = ItemIndex(model, projection=projection)
-    else:
-        if projection is not None and not index.owns_projection(projection):
-            raise ValueError("score_topk: index was built with another projection; pass the "
-                             "projection to ItemIndex and leave it out here")
-        if not index.valid_for(model):   # parameters changed since the index was built
-            index = ItemIndex(model, items=index.ids, projection=index.projection)
+    index = _resolve_index(model, index, projection, "score_topk")
     dev = index.p.device
     _check_exclude(exclude, model.num_users, model.num_products, dev)
     uid = user_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
@@ -887,14 +898,7 @@ def score_rank(model, user_ids: torch.Tensor, item_ids: torch.Tensor,
     _check_exclude(exclude, model.num_users, model.num_products)
     hour = _check_hour(hour, user_ids.numel())
     _check_rank(user_ids, item_ids, model.num_products, exclude, index)
-    if index is None:
-        index = ItemIndex(model, projection=projection)
-    else:
-        if projection is not None and not index.owns_projection(projection):
-            raise ValueError("score_rank: index was built with another projection; pass the "
-                             "projection to ItemIndex and leave it out here")
-        if not index.valid_for(model):   # parameters changed since the index was built
-            index = ItemIndex(model, projection=index.projection)
+    index = _resolve_index(model, index, projection, "score_rank")
     dev = index.p.device
     _check_exclude(exclude, model.num_users, model.num_products, dev)
     uid = user_ids.to(device=dev, dtype=torch.int64).contiguous()
@@ -905,15 +909,11 @@ def score_rank(model, user_ids: torch.Tensor, item_ids: torch.Tensor,
                 torch.empty(0, dtype=torch.int64, device=dev))
     I, qd = index.p.shape
     st = _lib.stream_ptr(dev)
-    table = model.mf_embedding_collection.embedding_bags["user_id"].weight
     q = torch.empty(n, qd, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     seen = dict(seen=exclude, users=uid) if exclude is not None else {}
     if hour is None:
-        _lib.call("ncf_score_queries", ptr(uid), n, ptr(table), model.num_users,
-                  model.mf_embedding_dim, ptr(model.mf_norm.weight), ptr(model.mf_norm.bias),
-                  LN_EPS, ptr(model.mf_output.weight), ptr(model.final[0].weight), ptr(q),
-                  ptr(err), st)
+        _queries(model, uid, n, q, err, st)
         place = _rank_places(q, index.p, index.bias, held, err=err, **seen)
     else:
         # one query launch for every row (the kernel scales row r by its own hour's s_h); the
@@ -921,10 +921,7 @@ def score_rank(model, user_ids: torch.Tensor, item_ids: torch.Tensor,
         hours = hour.to(device=dev, dtype=torch.int64).contiguous() \
             if isinstance(hour, torch.Tensor) else torch.full((n,), hour, dtype=torch.int64,
                                                               device=dev)
-        _lib.call("ncf_score_queries_hour", ptr(uid), ptr(hours), n, ptr(table), model.num_users,
-                  model.mf_embedding_dim, ptr(model.mf_norm.weight), ptr(model.mf_norm.bias),
-                  LN_EPS, ptr(model.mf_output.weight), ptr(model.final[0].weight),
-                  ptr(index.hour_table()), ptr(q), ptr(err), st)
+        _queries(model, uid, n, q, err, st, hours, index.hour_table())
         groups = group_by_hour(hours)
         place = torch.empty(n, dtype=torch.int64, device=dev)
         for h, pos in groups:
@@ -935,13 +932,7 @@ def score_rank(model, user_ids: torch.Tensor, item_ids: torch.Tensor,
             else:
                 sub = dict(seen=exclude, users=uid[pos]) if exclude is not None else {}
                 place[pos] = _rank_places(q[pos], index.p, bias_h, held[pos], err=err, **sub)
-    flags = int(err.item())
-    if flags & 1:
-        raise IndexError("score_rank: user id out of range of the embedding table")
-    if flags & 2:
-        raise IndexError("score_rank: hour outside [0, 24)")
-    if flags & 4:
-        raise IndexError("score_rank: item id out of range of the catalogue")
+    _raise_flags(int(err.item()), "score_rank")
     candidates = torch.full((n,), I, dtype=torch.int64, device=dev)
     if exclude is not None:
         candidates -= exclude.lengths[uid]
@@ -983,11 +974,7 @@ class GraphedScorer:
         self.exclude = exclude
         # the hour the static buffers hold (None: the hour=None pipeline, captured without them)
         self.hour = None if hour is None else _one_hour(hour, self.n)
-        if index is not None and projection is not None and not index.owns_projection(projection):
-            raise ValueError("GraphedScorer: index was built with another projection")
-        self.index = index if index is not None and index.valid_for(model) else ItemIndex(
-            model, items=None if index is None else index.ids,
-            projection=projection if index is None else index.projection)
+        self.index = _resolve_index(model, index, projection, "GraphedScorer")
         self._capture()
 
     def _capture(self):
@@ -1033,9 +1020,9 @@ class GraphedScorer:
                 raise ValueError("this GraphedScorer was captured for hour=None; build it with "
                                  "hour= to score at an hour")
             hour = _one_hour(hour, uid.numel())
-        if not self.index.valid_for(self.model):
-            self.index = ItemIndex(self.model, items=self.index.ids,
-                                   projection=self.index.projection)
+        index = _resolve_index(self.model, self.index, None, "GraphedScorer")
+        if index is not self.index:   # rebuilt: the parameters changed since the capture
+            self.index = index
             if hour is not None:
                 self.hour = hour
             self._capture()
@@ -1048,8 +1035,7 @@ class GraphedScorer:
         run.err.zero_()
         self.graph.replay()
         over, err = self.flags.tolist()
-        if err:
-            raise IndexError("score_topk: user id out of range of the embedding table")
+        _raise_flags(err, "score_topk")
         if over:
             run.redo_overflow(_lib.stream_ptr(run.uid.device))
             out = run.result()
@@ -1097,12 +1083,8 @@ def sharded_score_topk(model, user_ids: torch.Tensor, k: int = 10,
     r = dist.get_rank(group) if dist.is_initialized() else 0
     if local_topk is None:
         hour = _check_hour(hour, user_ids.numel())
-        if index is not None and projection is not None and \
-                not index.owns_projection(projection):
-            raise ValueError("sharded_score_topk: index was built with another projection")
-        if index is None or not index.valid_for(model):
-            index = ItemIndex(model, items=shard_items(model.num_products, W, r),
-                              projection=projection if index is None else index.projection)
+        index = _resolve_index(model, index, projection, "sharded_score_topk",
+                               items=lambda: shard_items(model.num_products, W, r))
         kk = min(k, index.p.shape[0])
 
         def local_topk(u, _k):

@@ -2177,7 +2177,7 @@ def test_sample_group_maxima_same_topk(k, monkeypatch):
 @pytest.mark.parametrize("k,cap", [(100, 8192), (40, 8192), (100, 4096)])
 def test_rank_j_threshold_equals_kth_threshold(k, cap, monkeypatch):
     """Rank-j thresholds (the sample's 16th largest logit over a sample ~k/16 times smaller,
-    the selection verified per user by ncf_score_select_rescored's thr_check) against the
+    the selection verified per user by the re-scoring select's thr_check) against the
     sample's k-th: the same top-k items and score bits.  The sample floor is lowered so the
     rank-j plan applies at 100003 items (it does from ~0.8M items at k = 100 by default)."""
     from ncf_amd import scoring

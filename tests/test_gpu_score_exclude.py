@@ -1,5 +1,5 @@
 """Top-k scoring that leaves out the items each user has already seen (``exclude=SeenItems``):
-the selects' exclusion (ncf_score_select_excl / ncf_score_select_rescored_excl), the exact
+the select's exclusion (ncf_score_select with its exclusion arguments), the exact
 re-run of users whose seen items reach into their top k, shards, the captured graph, and
 metrics.full_ranking_metrics.  Runs on a real MI355X only (marker ``gpu``).
 
@@ -327,7 +327,7 @@ def test_graphed_scorer_with_exclude(k, cap, shard):
 
 # --------------------------------------------------------------------------------- 8. D = 128
 def test_exclude_d128_vs_oracle():
-    """The fp32 scan and the select without re-scoring (ncf_score_select_excl): histories of
+    """The fp32 scan and the select without re-scoring (exclusion only): histories of
     0..20 random items, and every fourth user has seen its own top 10."""
     U, I, k = 64, 3001, 10
     m = _model(U, I, 41, 128, 128, 32, [256, 128, 64], 4, 0.2, 4)
@@ -434,7 +434,7 @@ def test_sampler_seen_shares_storage():
 
 # ------------------------------------------- 11. an overflowed list that lost its k candidates
 def test_select_excl_overflow_flags_at_the_c_abi():
-    """ncf_score_select_excl on hand-made lists that overflowed (count > cap = 16, K = 4): with
+    """ncf_score_select (exclusion) on hand-made lists that overflowed (count > cap = 16, K = 4): with
     two seen items the 4th remaining logit comes back as the re-run's threshold (flag 1); with 14
     seen only two candidates remain, which bound nothing: flag 2, the threshold untouched."""
     from ncf_amd import _lib
@@ -450,9 +450,9 @@ def test_select_excl_overflow_flags_at_the_c_abi():
     out_s = torch.empty(2, K, device=DEV)
     out_i = torch.empty(2, K, dtype=torch.int64, device=DEV)
     flag = torch.zeros(2, dtype=torch.int32, device=DEV)
-    _lib.call("ncf_score_select_excl", None, 2, ptr(count), ptr(cand), cap, K, ptr(out_s),
-              ptr(out_i), ptr(thr), ptr(flag), None, ptr(uid), 2, ptr(seen.offsets),
-              ptr(seen.items), None, _lib.stream_ptr(DEV))
+    _lib.call("ncf_score_select", None, 2, ptr(count), ptr(cand), cap, K, None, None, None, 0,
+              None, 0.0, ptr(out_s), ptr(out_i), ptr(thr), ptr(flag), None, ptr(uid), 2,
+              ptr(seen.offsets), ptr(seen.items), None, _lib.stream_ptr(DEV))
     torch.cuda.synchronize()
     assert flag.tolist() == [1, 2]
     assert thr.tolist() == [11.0, 123.0]

@@ -254,6 +254,78 @@ def test_identical_catalogue(D):
         assert place.cpu().tolist() == held.tolist()
 
 
+@pytest.mark.parametrize("D", [64, 128])
+def test_three_scans_and_the_pair_kernel_are_one_arithmetic(D):
+    """logit(r, j) of 33 rows (a full wave of rows plus one) x 600 items taken four ways, all
+    built on csrc/scan_tile_dev.h: (a) ncf_rank_pair_logits over all 19,800 pairs; (b)
+    ncf_score_collect with every threshold at -inf and cap = 600 (one row block: item blocks of
+    224, 224 and 152 items, the last ending in a partial tile); (c) ncf_rank_scan in item blocks
+    of 32 against rank_ref on (a)'s logits; (d) with a zero bias, the 128 similarities
+    ncf_nn_scan keeps per query.  (a) == (b) and (a) == (d) bit for bit, (c)'s places exact,
+    and (a) within the fma chain's bound (D + 2) 2^-24 (sum_k |q_k p_k| + |bias_j|) of the
+    float64 dot product."""
+    from ncf_amd import _lib
+    from ncf_amd._lib import ptr
+    n, I, K = 33, 600, 128
+    g = torch.Generator().manual_seed(900 + D)
+    q, p, bias = torch.randn(n, D, generator=g), torch.randn(I, D, generator=g), \
+        torch.randn(I, generator=g)
+    held = torch.randint(0, I, (n,), generator=g)
+    qd, pd, bd = q.to(DEV), p.to(DEV), bias.to(DEV)
+    st = _lib.stream_ptr(DEV)
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    rows = torch.arange(n, dtype=torch.int32, device=DEV).repeat_interleave(I)
+    pair_items = torch.arange(I, dtype=torch.int32, device=DEV).repeat(n)
+
+    def pair_logits(b):                                                    # (a)
+        out = torch.empty(n * I, device=DEV)
+        _lib.call("ncf_rank_pair_logits", ptr(qd), n, ptr(rows), ptr(pair_items), n * I, ptr(pd),
+                  ptr(b), I, D, ptr(out), ptr(err), st)
+        return out.view(n, I)
+
+    a = pair_logits(bd)
+    # the sanity bound, float64
+    q64, p64, b64 = q.double(), p.double(), bias.double()
+    bound = (D + 2) * 2.0 ** -24 * (q64.abs() @ p64.abs().T + b64.abs()[None, :])
+    dev = (a.cpu().double() - (q64 @ p64.T + b64[None, :])).abs()
+    print(f"D={D}: max |(a) - float64| / bound = {float((dev / bound).max()):.3f}")
+    assert bool((dev <= bound).all())
+
+    # (b) the collect at -inf: every user's list is the whole catalogue
+    thr = torch.full((n,), float("-inf"), device=DEV)
+    count = torch.zeros(n, dtype=torch.int32, device=DEV)
+    cand = torch.full((n, I, 2), -1, dtype=torch.int32, device=DEV)
+    _lib.call("ncf_score_collect", ptr(qd), None, n, ptr(pd), ptr(bd), I, D, ptr(thr), I,
+              ptr(count), ptr(cand), st)
+    assert count.tolist() == [I] * n
+    order = torch.argsort(cand[:, :, 1], dim=1)
+    assert torch.equal(torch.gather(cand[:, :, 1], 1, order),
+                       torch.arange(I, dtype=torch.int32, device=DEV).expand(n, I))
+    b_bits = torch.gather(cand[:, :, 0], 1, order)
+    assert torch.equal(b_bits, a.view(torch.int32))
+
+    # (c) the rank scan in 19 item blocks, from (a)'s targets
+    held32 = held.to(device=DEV, dtype=torch.int32)
+    target = a[torch.arange(n, device=DEV), held.to(DEV)].contiguous()
+    places = torch.zeros(n, dtype=torch.int32, device=DEV)
+    _lib.call("ncf_rank_scan", ptr(qd), n, ptr(pd), ptr(bd), I, D, ptr(target), ptr(held32), 32,
+              ptr(places), st)
+    assert places.cpu().tolist() == R.places(a.cpu().numpy(), held.numpy()).tolist()
+
+    # (d) the neighbour scan's kept similarities, bias 0
+    a0 = pair_logits(torch.zeros(I, device=DEV))
+    sim = torch.empty(n, 1, K, device=DEV)
+    item = torch.empty(n, 1, K, dtype=torch.int64, device=DEV)
+    _lib.call("ncf_nn_scan", ptr(qd), n, 0, ptr(pd), I, D, None, None, None, I, 1, K, ptr(sim),
+              ptr(item), st)
+    torch.cuda.synchronize()
+    item = item.view(n, K)
+    assert int(item.min()) >= 0 and int(item.max()) < I
+    want = torch.gather(a0, 1, item) + 0.0
+    assert torch.equal((sim.view(n, K) + 0.0).view(torch.int32), want.view(torch.int32))
+    assert int(err.item()) == 0
+
+
 # ---- 4. hour
 
 @functools.lru_cache(maxsize=None)

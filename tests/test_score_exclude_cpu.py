@@ -122,9 +122,18 @@ def test_exclude_is_keyword_only_and_pinned_signatures_keep_their_positions():
 
 
 def test_new_entry_points_are_declared():
+    """One select entry: its SIGNATURES argument count is the header declaration's, and the
+    three names it replaced are in neither."""
+    import os
+    import re
     from ncf_amd import _lib
-    for name in ("ncf_score_select_excl", "ncf_score_select_rescored_excl"):
-        assert name in _lib.SIGNATURES
-    # the existing selects keep their argument lists
-    assert len(_lib.SIGNATURES["ncf_score_select"][1]) == 11
-    assert len(_lib.SIGNATURES["ncf_score_select_rescored"][1]) == 18
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "ncf_hip.h")) as f:
+        header = f.read()
+    decl = re.search(r"\bint\s+ncf_score_select\s*\(([^)]*)\)\s*;", header)
+    assert decl is not None
+    assert len(_lib.SIGNATURES["ncf_score_select"][1]) == len(decl.group(1).split(","))
+    for name in ("ncf_score_select_rescored", "ncf_score_select_excl",
+                 "ncf_score_select_rescored_excl"):
+        assert name not in _lib.SIGNATURES
+        assert name not in header
