@@ -569,6 +569,30 @@ int ncf_hour_grad(const int64_t* hour, int64_t n, const float* dte, int64_t ld, 
                   int64_t ld_add, int64_t dim, float* grad_hour, float* workspace,
                   int64_t workspace_floats, void* stream);
 
+/* ---- global gradient-norm clipping (trainer.py:278-283, torch.nn.utils.clip_grad_norm_),
+ * grad_clip.hip.  The gradients are a list of at most NCF_GRAD_CLIP_MAX_SEGS segments, read by
+ * value at the call: data[rows, dim] fp32, dense (leading dimension dim); with rows_dev != NULL
+ * only the first min(*rows_dev, rows) rows are valid (a device int32, read on the device: the
+ * compact table gradients of a backward) and the rest is never read or written.
+ * ncf_grad_clip: out[0] = the norm of all valid elements (norm_kind 0: 2-norm, 1: largest
+ * absolute value), out[1] = c = min(1, max_norm / (out[0] + 1e-6)), and every valid element is
+ * multiplied by c in place (one fp32 multiply; nothing is stored when c == 1).  max_norm = +inf
+ * computes the norm only (out[1] = 1).  max_norm <= 0 or NaN, or a bad list: NCF_ERR_ARG.
+ * Deterministic: two launches, fp64 partial sums per chunk of ncf_grad_clip_chunk() floats of
+ * each segment's capacity, added in a fixed order; no atomics.  workspace: 8-byte aligned,
+ * ncf_grad_clip_workspace(segs, nsegs) bytes (0: a bad list).                                 */
+typedef struct ncf_grad_seg {
+  float* data;
+  const int32_t* rows_dev;
+  int64_t rows;
+  int64_t dim;
+} ncf_grad_seg;
+#define NCF_GRAD_CLIP_MAX_SEGS 32
+int64_t ncf_grad_clip_chunk(void);
+int64_t ncf_grad_clip_workspace(const ncf_grad_seg* segs, int nsegs);
+int ncf_grad_clip(const ncf_grad_seg* segs, int nsegs, int norm_kind, double max_norm,
+                  void* workspace, int64_t workspace_bytes, float* out, void* stream);
+
 /* ---- a7: MLP tower row ops (ReLU -> LayerNorm -> Dropout), architecture.py:233-239 --------
  * Backward also returns grad_bias = column sums of grad_lin (the bias gradient of the Linear
  * that feeds the ReLU; nullable).                                                            */

@@ -215,6 +215,9 @@ SIGNATURES = {
     "ncf_hour_grad_workspace": (I64, [I64, I64]),
     "ncf_item_scale_bwd": (I32, [P, I64, P, P, I64, I64, P, P, P, P, F32, P, F32, P, P, P, P, P]),
     "ncf_hour_grad": (I32, [P, I64, P, I64, P, I64, I64, P, P, I64, P]),
+    "ncf_grad_clip_chunk": (I64, []),
+    "ncf_grad_clip_workspace": (I64, [P, I32]),
+    "ncf_grad_clip": (I32, [P, I32, I32, F64, P, I64, P, P]),
 }
 
 
@@ -237,6 +240,14 @@ class WgradDesc(ctypes.Structure):
 
 
 WGRAD_GROUP_MAX = 8
+
+
+class GradSeg(ctypes.Structure):
+    """ncf_grad_seg (include/ncf_hip.h)."""
+    _fields_ = [("data", P), ("rows_dev", P), ("rows", I64), ("dim", I64)]
+
+
+GRAD_CLIP_MAX_SEGS = 32
 
 
 class MlpLayer(ctypes.Structure):

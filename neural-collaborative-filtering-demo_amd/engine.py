@@ -1058,6 +1058,7 @@ class NCFEngine:
         uq_u, uq_i = uniq if uniq is not None else (w.uniq_u, w.uniq_i)
         d_rows = rows or (m.num_users, m.num_products)
         w.slots_set = False
+        w.sent_rows = grad_rows is not None    # (table gradients in the caller's buffer, not w.G)
         ev = getattr(w, "dedup_ev", None)
         if ev is not None:   # the id sort forked beside the forward (deferred._prepare_claim)
             ev.wait(st)

@@ -2,7 +2,8 @@
 
 ``ModelTrainer.train_epoch`` mirrors the reference loop (src/model/trainer.py:216-337): per batch
 ``model(features)`` -> ``nn.BCELoss`` -> ``zero_grad`` -> ``backward`` -> no clipping (the
-reference's ``hasattr(dict, 'gradient_clipping')`` guard at :279 is always False) ->
+reference's ``hasattr(dict, 'gradient_clipping')`` guard at :279 is always False;
+``clip_gradients=True`` clips there with ``ncf_amd.clip_grad_norm_``) ->
 ``Adam.step`` with lr / weight_decay from the config (:54-75).  The BigQuery / DataLoader side of
 the reference trainer is out of scope; batches are (KeyedJaggedTensor, targets[N, 1]) exactly as
 ``collate_recommender_batch`` builds them (src/model/data_prep.py:230-320).
@@ -11,6 +12,7 @@ the reference trainer is out of scope; batches are (KeyedJaggedTensor, targets[N
 BCE + backward kernels, fused Adam — identical math, one kernel sequence on one stream.  It is
 what the benchmark times (and what a production trainer uses).
 """
+import ctypes
 import logging
 import weakref
 from typing import Any, Dict, Optional  # noqa: F401
@@ -19,8 +21,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import clip
 from . import deferred as deferred_mod
 from ._lib import ptr
+from .clip import clip_grad_norm_
 
 log = logging.getLogger(__name__)
 
@@ -98,14 +102,29 @@ class FusedTrainStep:
     it: ~50 launches for the price of one, no per-step host work.  Every step-dependent value
     (Adam step, rolling-sweep slice, dropout stream) then lives in a device ``ncf_step_clock``
     that the last kernel of the step advances (``clock=True`` uses the clock without capture;
-    the two are bit-identical).  Inputs are copied into static buffers before each replay."""
+    the two are bit-identical).  Inputs are copied into static buffers before each replay.
+
+    ``max_grad_norm`` clips the global 2-norm of the step's gradients (the four compact table
+    gradients and the flat dense buffer) to that value before any Adam reads them, as
+    ``clip_grad_norm_`` does between ``backward()`` and ``step()``; the step's norm is
+    ``last_grad_norm`` (a 0-dim device tensor).  Such a step runs the table apply as its own launch
+    behind the clip (not inside the embedding backward) and leaves the next batch's catch-up to
+    the next step.  ``None`` (default): the step as it is without clipping."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
                  deferred: bool = True, sweep_every: int = SWEEP_EVERY, graph: bool = False,
                  clock: Optional[bool] = None, warmup: int = 2, concurrent: Optional[bool] = None,
-                 overlap_sweep: Optional[bool] = None, table_dtype: torch.dtype = torch.float32):
+                 overlap_sweep: Optional[bool] = None, table_dtype: torch.dtype = torch.float32,
+                 max_grad_norm: Optional[float] = None):
         self.model = model
         self.deferred = None
+        # global gradient-norm clipping (clip.py, DESIGN §20): the 2-norm over the four compact
+        # table gradients and the flat dense buffer, scaled in place before any Adam reads them
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be > 0 (or None), got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None     # the last step's total norm (0-dim device tensor)
+        self._clip_ws = None
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         if model.mf_embedding_dim != model.mlp_embedding_dim:
             # the deferred schedule steps an MF and an MLP table as one pair of one width: the
@@ -191,6 +210,24 @@ class FusedTrainStep:
         if self.deferred is not None:
             self.deferred.lr = self._lr
 
+    @property
+    def _fuse_apply(self) -> bool:
+        """Whether this step runs the table apply inside the embedding backward: not when it
+        clips (the gradients must be complete, and scaled, before any row steps)."""
+        return FUSE_APPLY and self.deferred is not None and self.max_grad_norm is None
+
+    def _clip(self, w):
+        """ncf_grad_clip over this step's compact table gradients and the flat dense buffer (no
+        step-dependent host argument: captured as it stands)."""
+        eng = self.model.engine
+        dev = eng.flat.device
+        segs = clip.table_segments(w) + [(eng.flat_grad, None, 1, eng.flat_grad.numel())]
+        need = _lib.query("ncf_grad_clip_workspace", ctypes.addressof(clip.seg_array(segs)),
+                          len(segs))
+        if self._clip_ws is None or self._clip_ws.numel() * 8 < need:   # (another batch size)
+            self._clip_ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        self.last_grad_norm = clip.run(segs, 0, self.max_grad_norm, dev, ws=self._clip_ws)[0]
+
     def _body(self, user_ids, item_ids, targets, M):
         m = self.model
         eng = m.engine
@@ -204,7 +241,7 @@ class FusedTrainStep:
         d = self.deferred
         side = (d.side_stream() if EARLY_REDUCE and d is not None and d.overlap and not self.graph
                 else None)
-        fa = d.fused_apply_args(w) if FUSE_APPLY and d is not None else None
+        fa = d.fused_apply_args(w) if self._fuse_apply else None
         # (the late catch-up is read when the table apply has been queued, not here: the sweep
         # fork, and with it the next batch's prefetch, may sit in the backward — "mlp_bwd")
         done = self._tables_done if fa is not None else None
@@ -212,6 +249,9 @@ class FusedTrainStep:
                      bf16=self.bf16, reduce_side=side, fused_apply=fa, tables_done=done)
         st = _lib.stream_ptr(eng.flat.device)
         b1, b2 = self.betas
+        if self.max_grad_norm is not None:
+            eng.join_reductions()            # (every dense gradient is in the flat buffer)
+            self._clip(w)
         if self.deferred is not None:
             self.deferred.apply(w, st)
         elif self.bf16:      # dense bf16 sweep (the reference schedule of the bf16 tables)
@@ -251,7 +291,7 @@ class FusedTrainStep:
             return
         if FUSED_TAIL and not EARLY_REDUCE:
             # (_late_next is only ever set by an eager clocked step whose prefetch sorted the
-            # next batch behind the sweep, with LATE_CATCHUP and FUSE_APPLY on)
+            # next batch behind the sweep, with LATE_CATCHUP on and the apply fused: _fuse_apply)
             self.model.engine.tail_catchup = late
         else:
             self._late_catchup(*late)
@@ -311,7 +351,7 @@ class FusedTrainStep:
             # its rows this step does not touch caught up through this step behind the sort
             # (early), or once this step's apply has run (late: _late_catchup)
             if not self.deferred.early_catchup(s, uid.numel(), side.cuda_stream) and \
-                    deferred_mod.LATE_CATCHUP and FUSE_APPLY:
+                    deferred_mod.LATE_CATCHUP and self._fuse_apply:
                 self._late_next = (s, uid.numel())
             # the sweep's done-event re-recorded behind the sort: the step's sweep join (before
             # the clock advance) then orders the sort too, and the next step waits for nothing
@@ -545,7 +585,12 @@ class FusedTrainStep:
 class ModelTrainer:
     """Reference-compatible trainer (src/model/trainer.py:27-95, 216-337) minus BigQuery I/O."""
 
-    def __init__(self, model: nn.Module, config: Dict[str, Any], num_gpus: int = 1):
+    def __init__(self, model: nn.Module, config: Dict[str, Any], num_gpus: int = 1,
+                 clip_gradients: bool = False):
+        # clip_gradients: clip to config["gradient_clipping"] where the reference intends to
+        # (trainer.py:278-283).  Off by default: the reference's guard there,
+        # hasattr(dict, 'gradient_clipping'), is always False, so it never clips
+        self.clip_gradients = bool(clip_gradients)
         required = {"num_users", "num_products", "batch_size", "learning_rate"}
         missing = required - set(config.keys())
         if missing:
@@ -586,6 +631,9 @@ class ModelTrainer:
             loss = self.criterion(outputs, targets)
             self.optimizer.zero_grad()
             loss.backward()
+            if self.clip_gradients and "gradient_clipping" in self.config:
+                # (the model itself: its parameter list is kept between calls, clip.py)
+                clip_grad_norm_(self.model, self.config["gradient_clipping"])
             self.optimizer.step()
             total_loss = loss.detach() if total_loss is None else total_loss + loss.detach()
             num_batches += 1
