@@ -10,7 +10,8 @@ OBJ="${NCF_OBJ:-$SRC/build}"
 mkdir -p "$OBJ"
 rm -f "$OBJ"/*.o
 FLAGS=(--offload-arch=gfx950 -O3 -fPIC -std=c++17 -I"$SRC" -I"$ROOT/include" -Wall -Wno-unused-function ${NCF_EXTRA_FLAGS:-})
-# build identity compiled into capi.hip (ncf_build_info; checked by _lib.load())
+# build identity compiled into capi.hip (ncf_build_info; checked by _lib.load()): the hash of
+# the header's entry points and of the sources
 ABI_HASH="$(python3 "$ROOT/neural-collaborative-filtering-demo_amd/_abi.py" abi)"
 SRC_HASH="$(python3 "$ROOT/neural-collaborative-filtering-demo_amd/_abi.py" src "$SRC")"
 NCF_FLAGS_capi="${NCF_FLAGS_capi:-} -DNCF_ABI_HASH=\"$ABI_HASH\" -DNCF_SRC_HASH=\"$SRC_HASH\""
@@ -25,8 +26,9 @@ for p in "${pids[@]}"; do wait "$p"; done
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC "$OBJ"/*.o -o "$OUT.tmp"
 mv "$OUT.tmp" "$OUT"
 echo "built $OUT"
-# CPython fast-call binding of the C-ABI (generated from _lib.SIGNATURES; ctypes stays the
-# loader and hands it the resolved entry points)
+# CPython fast-call binding of the C-ABI (generated from include/ncf_hip.h through
+# _abi.parse_header, as the ctypes table is; ctypes stays the loader and hands it the resolved
+# entry points)
 PYINC="$(python3 -c 'import sysconfig; print(sysconfig.get_paths()["include"])')"
 PYSUF="$(python3 -c 'import sysconfig; print(sysconfig.get_config_var("EXT_SUFFIX"))')"
 python3 "$GEN" "$OBJ/_ncffast.c"

@@ -15,6 +15,21 @@
  *     thread-local message.  Stateless and re-entrant; ordering is by stream.
  *   - ids outside [0, rows) never read out of bounds: they read row 0 and set bit 0 of the
  *     caller's device `err_flag` (the host raises IndexError, like nn.EmbeddingBag).
+ *
+ * Declaration conventions
+ *   The Python binding (ctypes table, struct mirrors, limits, fast-call wrappers) is generated from
+ *   this file by _abi.parse_header(), which refuses a declaration it does not understand instead
+ *   of skipping it.  It accepts:
+ *   - entry points `T name(args);` with T one of int, int32_t, int64_t, uint64_t, float, double
+ *     or `const char*`; arguments of those scalar types by value, or pointers (`T*`, `T**`, with
+ *     `const` anywhere; every pointer binds as void*); `(void)` for none; a declaration may span
+ *     lines.  No function-pointer arguments, no structs by value;
+ *   - `typedef struct [__attribute__((aligned(N)))] name { ... } name;` whose fields are those
+ *     scalars, pointers, arrays `T f[BOUND]` or an earlier struct of this file, several
+ *     declarators per statement allowed (`float *p0, *m0;`).  No bit-fields, no nested bodies;
+ *   - `#define NCF_NAME <integer>` (decimal, hex, parenthesised, or a sum with earlier defines,
+ *     which is also what an array BOUND may be).  No other macros, no conditionals besides the
+ *     include guard and the extern "C" block.
  */
 #ifndef NCF_HIP_H
 #define NCF_HIP_H
@@ -50,9 +65,10 @@ int64_t ncf_adam_sweep_set_blocks(int64_t per_cu);
 int ncf_version(void);
 const char* ncf_last_error(void);
 int ncf_device_count(void);
-/* Build identity: "abi=<16 hex> src=<16 hex>", the hash of the ctypes table the library was built
- * against (_lib.SIGNATURES) and of the kernel sources it was compiled from (_abi.py).  The
- * loader refuses a library whose hashes differ from the Python side and sources beside it.
+/* Build identity: "abi=<16 hex> src=<16 hex>", the hash of this header's entry points (names,
+ * result and argument types, in order) at build time and of the kernel sources the library was
+ * compiled from (_abi.py).  The loader refuses a library whose hashes differ from the header and
+ * sources beside the package.
  * (Packaging plumbing: the reference is pure Python and has no compiled library to match.)   */
 const char* ncf_build_info(void);
 
@@ -726,6 +742,8 @@ int ncf_scatter_compact_rows(float* dense_grad, int64_t dim, const int64_t* uniq
  * over a narrower table are padded the same way).  Pipeline: queries -> sample logits (ncf_gemm_f32
  * with a strided B) -> ncf_score_kth thresholds -> ncf_score_collect candidates ->
  * ncf_score_select top-K (overflow[slot] = 1: re-run 3-4 for those slots with the returned thr). */
+#define NCF_SCORE_KTH_LDS_MAX 38912 /* ncf_score_kth / _kth16: the longest LDS-resident sample */
+#define NCF_SCORE_SELECT_MAX 8192   /* ncf_score_select's cap, ncf_score_merge's L and K */
 int ncf_score_queries(const int64_t* user_ids, int64_t n, const float* mf_user, int64_t rows,
                       int64_t dim, const float* mf_gamma, const float* mf_beta, float eps,
                       const float* mf_out_w, const float* final_w, float* queries, int* err_flag,

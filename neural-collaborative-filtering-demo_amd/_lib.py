@@ -1,4 +1,6 @@
-"""ctypes binding of libncf_hip.so (include/ncf_hip.h).
+"""ctypes binding of libncf_hip.so, generated at import from include/ncf_hip.h
+(``_abi.parse_header``): the entry points' types, the struct mirrors and the limits are read from
+the header, which has to sit beside the package, as it does for the build.
 
 The library is built for gfx950 by ``build_ext.sh`` (driven by ``__graft_entry__.build()``) and
 lives next to this file.  It links ``libamdhip64.so.7``; ``torch`` is imported first so the
@@ -13,6 +15,8 @@ import os
 import threading
 
 import torch  # noqa: F401  (must precede the CDLL: binds libncf_hip to torch's HIP runtime)
+
+from . import _abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _DEFAULT_LIB = os.path.join(_HERE, "libncf_hip.so")
@@ -35,268 +39,87 @@ F32 = ctypes.c_float
 F64 = ctypes.c_double
 U64 = ctypes.c_uint64
 
-# name -> (restype, argtypes); mirrors include/ncf_hip.h exactly
-SIGNATURES = {
-    "ncf_version": (I32, []),
-    "ncf_last_error": (ctypes.c_char_p, []),
-    "ncf_event_create": (I32, [P]),
-    "ncf_event_create_scoped": (I32, [P, I32]),
-    "ncf_event_destroy": (I32, [P]),
-    "ncf_event_record": (I32, [P, P]),
-    "ncf_stream_wait_event": (I32, [P, P]),
-    "ncf_event_synchronize": (I32, [P]),
-    "ncf_memcpy_async": (I32, [P, P, I64, P]),
-    "ncf_device_count": (I32, []),
-    "ncf_build_info": (ctypes.c_char_p, []),
-    "ncf_gather_ln_gmf_ld_fwd": (I32, [P, P, I64, P, P, P, P, I64, I64, I64, I64, P, P, P, P, P, P,
-                                       F32, I64, P, P, P, P, P, P, P]),
-    "ncf_gather_ln_gmf_fwd": (I32, [P, P, I64, P, P, P, P, I64, I64, I64, P, P, P, P, P, P, F32,
-                                    P, P, P, P, P, P, P]),
-    "ncf_gather_ln_gmf_scaled_fwd": (I32, [P, P, I64, P, P, P, P, I64, I64, I64, P, P, P, P, P, P,
-                                           F32, P, F32, I64, P, P, P, P, P, P, P]),
-    "ncf_gather_ln_gmf_bf16_fwd": (I32, [P, P, I64, P, P, P, P, I64, I64, I64, P, P, P, P, P, P,
-                                         F32, I64, P, P, P, P, P, P, P]),
-    "ncf_gather_rows": (I32, [P, I64, P, I64, I64, P, P, F32, P, P, P]),
-    "ncf_bag_pool_fwd": (I32, [P, I64, P, I64, P, P, I64, I64, I32, P, P, P]),
-    "ncf_bag_pool_bwd_workspace": (I64, [I64, I64, I64]),
-    "ncf_bag_pool_bwd": (I32, [P, I64, P, I64, P, P, P, I64, I64, I32, P, P, P, I64, P]),
-    "ncf_gemm_f32": (I32, [I64, I64, I64, P, I64, I32, P, I64, I32, P, I64, P, I32, P]),
-    "ncf_gemm_splitk_workspace": (I64, [I64, I64, I32]),
-    "ncf_gemm_f32_splitk": (I32, [I64, I64, I64, P, I64, I32, P, I64, I32, P, I64, I32, P, I32,
-                                  P, I64, P, P]),
-    "ncf_gemm_direct": (I32, [I64, I64, I64, P, I64, I32, P, I64, I32, P, I64, P, I32, P]),
-    "ncf_gemm_rows": (I32, [I64, I64, I64, P, I64, P, I64, I32, P, I64, P, I32, P]),
-    "ncf_wgrad_grouped_workspace": (I64, [P, I32]),
-    "ncf_wgrad_grouped": (I32, [P, I32, P, I64, P, P]),
-    "ncf_reduce_batch_scratch": (I64, [P]),
-    "ncf_reduce_set_vec": (I64, [I64]),
-    "ncf_stream_spin": (I32, [I64, P]),
-    "ncf_adam_sweep_set_blocks": (I64, [I64]),
-    "ncf_dropout_rows": (I32, [P, I64, I64, I64, F32, U64, P, P, P]),
-    "ncf_reduce_batch": (I32, [P, P, I64, P]),
-    "ncf_colsum_workspace": (I64, [I64, I64]),
-    "ncf_colsum": (I32, [P, I64, I64, I64, P, I32, P, I64, P]),
-    "ncf_attention_fwd": (I32, [P, P, P, I64, I64, I64, I64, F32, U64, P, P, P, P]),
-    "ncf_attention_fwd_masked": (I32, [P, P, P, I64, I64, I64, I64, F32, U64, P, P, P, P, P]),
-    "ncf_attention_bwd": (I32, [P, P, P, P, P, I64, I64, I64, I64, F32, U64, P, P, P, P, P, P]),
-    "ncf_attention_x_fwd": (I32, [P, P, P, I64, I64, I64, I64, I64, F32, U64, P, P, P, P, P]),
-    "ncf_attention_x_bwd": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, F32, U64, P, P, P, P, P]),
-    "ncf_attn_block_supported": (I32, [I64, I64, I64]),
-    "ncf_mlp_fused_supported": (I32, [I64, I64, P]),
-    "ncf_attn_mlp_fused_supported": (I32, [I64, I64, I64, I64, P]),
-    "ncf_attn_mlp_fwd": (I32, [P, P, I64, I64, P, P, P, P, P, P, P, P, F32, U64, P, P, P, P, P, P,
-                               P, P, I64, P, F32, P, P, P, P, P, P, P, I32, P]),
-    "ncf_attn_mlp_bwd": (I32, [I64, I64, P, P, I64, P, F32, U64, P, P, P, I64, P, P, P, P, P, P,
-                               P, P, P, P, P, P, I64, P, P, P, P, I32, P]),
-    "ncf_attn_mlp_fwd_small": (I32, [P, P, I64, I64, P, P, P, P, P, P, P, P, F32, U64, P, P, P, P, P, P,
-                               P, P, I64, P, F32, P, P, P, P, P, P, P, I32, P]),
-    "ncf_attn_mlp_bwd_small": (I32, [I64, I64, P, P, I64, P, F32, U64, P, P, P, I64, P, P, P, P, P, P,
-                               P, P, P, P, P, P, I64, P, P, P, P, I32, P]),
-    "ncf_attn_mlp_bwd_workspace": (I64, [I64, I32]),
-    "ncf_attn_mlp_bwd_workspace_small": (I64, [I64, I32]),
-    "ncf_attn_mlp_fused_supported_small": (I32, [I64, I64, I64, I64, P]),
-    "ncf_alias_build": (I32, [P, I64, P, P]),
-    "ncf_group_metrics_workspace": (I64, [I64, I64]),
-    "ncf_group_metrics": (I32, [P, P, I64, I64, P, I64, F32, P, P, I64, P]),
-    "ncf_auc_count": (I32, [P, P, I64, P, I64, P, P]),
-    "ncf_embedding_export": (I32, [P, I64, P, I64, I64, P, P, F32, I32, P, P, P]),
-    "ncf_sample_negatives": (I32, [P, P, I64, I64, P, P, I64, P, P, I64, U64, I64, P, P, P, P, P]),
-    "ncf_mlp_fwd": (I32, [P, I64, I64, P, I64, P, F32, F32, U64, P, P, P, P, P, P, P, P, P]),
-    "ncf_mlp_fwd_bf16": (I32, [P, I64, I64, P, I64, P, F32, F32, U64, P, P, P, P, P, P, P, P, P]),
-    "ncf_mlp_bwd_bf16": (I32, [P, I64, I64, P, P, I64, P, F32, U64, P, P, P, P, I64, P, P]),
-    "ncf_mlp_fwd_split": (I32, [P, I64, I64, P, I64, P, F32, F32, U64, P, P, P, P, P, P, P, P, P]),
-    "ncf_mlp_bwd_split": (I32, [P, I64, I64, P, P, I64, P, F32, U64, P, P, P, P, I64, P, P]),
-    "ncf_mlp_bwd_workspace": (I64, [I64]),
-    "ncf_mlp_bwd": (I32, [P, I64, I64, P, P, I64, P, F32, U64, P, P, P, P, I64, P, P]),
-    "ncf_attn_block_fwd": (I32, [P, P, I64, I64, I64, I64, P, P, P, P, P, P, P, P, F32, U64, P,
-                                 P, P, P, P, P, P, P, P]),
-    "ncf_attn_block_bwd_workspace": (I64, [I64]),
-    "ncf_attn_block_rc_supported": (I32, [I64, I64, I64]),
-    "ncf_attn_block_bwd_rc": (I32, [P, P, P, I64, I64, I64, I64, P, P, P, P, P, P, P, F32, U64, P,
-                                    P, P, I64, P, P, P, P, P]),
-    "ncf_attn_block_bwd": (I32, [P, P, P, P, P, I64, I64, I64, I64, P, P, P, P, F32, U64, P, P,
-                                 P, P, P, P, I64, P, P, P, P, P, P, P, P]),
-    "ncf_relu_ln_dropout_fwd": (I32, [P, I64, I64, P, P, F32, F32, U64, P, P, P, P, P]),
-    "ncf_relu_ln_dropout_bwd_workspace": (I64, [I64, I64]),
-    "ncf_relu_ln_dropout_bwd": (I32, [P, P, P, P, P, I64, I64, F32, U64, P, P, P, P, P, P, I64,
-                                      P, P]),
-    "ncf_head_fwd": (I32, [P, I64, I64, P, P, P, P, P, P, P, P]),
-    "ncf_head_bwd_workspace": (I64, [I64, I64, I64]),
-    "ncf_head_bwd": (I32, [P, P, P, P, P, P, I64, I64, P, P, P, P, I64, P, P, P, P, P, P, P, P,
-                           P, P, P, F64, P, I64, P, P]),
-    "ncf_embedding_bwd_workspace": (I64, [I64, I64]),
-    "ncf_embedding_bwd": (I32, [P, P, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, F32, P, P,
-                                P, P, P, P, P, P, P, P, P, P, P, P, I64, P]),
-    "ncf_dedup_ids": (I32, [P, P, I64, I64, I64, I64, P, P, P, P, P, P, I64, P]),
-    "ncf_dedup_set_small_max": (I64, [I64]),
-    "ncf_dedup_ids2": (I32, [P, I64, I64, P, I64, I64, I64, P, P, P, P, P, P, I64, P]),
-    "ncf_dedup_inverse": (I32, [I64, I64, I64, I64, I64, P, P, P, I64, P]),
-    "ncf_shard_plan": (I32, [P, P, I64, I32, I64, I64, I64, P, P, I64, P, P]),
-    "ncf_shard_owner_prepare": (I32, [P, P, ctypes.c_int32, P, P, P, P, I64, I64, P, P, P, P, P,
-                                      P, P]),
-    "ncf_shard_owner_gather": (I32, [P, P, P, P, I64, P, P, I64, I64, P, P]),
-    "ncf_shard_owner_gradsum": (I32, [P, P, P, P, I64, I32, I64, P, P, P, P, P]),
-    "ncf_shard_rows": (I32, [P, P, P, P, I64, I64, P, P, P, P, I32, P]),
-    "ncf_comm_available": (I32, []),
-    "ncf_comm_unique_id": (I32, [P, I64]),
-    "ncf_comm_init": (I32, [P, I64, I32, I32, P]),
-    "ncf_comm_destroy": (I32, [P]),
-    "ncf_comm_alltoallv": (I32, [P, P, P, P, P, I64, P]),
-    "ncf_comm_allreduce_sum_f32": (I32, [P, P, I64, P]),
-    "ncf_embedding_bwd_reduce_rows": (I32, [I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, F32,
-                                            P, P, P, P, P, P, P, P, I64, I64, P, P, P, P, P, I64,
-                                            P, P]),
-    "ncf_embedding_bwd_reduce_apply_clock": (I32, [I64, I64, I64, I64, P, P, P, P, P, P, F32, P, P,
-                                                   P, P, P, P, P, P, P, P, P, I64, P, P, I32, P,
-                                                   P, F64, F64, F64, F64, P]),
-    "ncf_embedding_bwd_reduce": (I32, [I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, F32, P, P,
-                                       P, P, P, P, P, P, P, P, P, I64, P, P]),
-    "ncf_embedding_bwd_reduce_bf16": (I32, [I64, I64, I64, I64, P, P, P, P, P, P, P, P, P, P, F32,
-                                            P, P, P, P, P, P, P, P, P, P, P, I64, P, P]),
-    "ncf_slot_reset": (I32, [P, P, I32, P, I64, P]),
-    "ncf_scatter_compact_rows": (I32, [P, I64, P, P, I32, P, I64, P]),
-    "ncf_adam_table": (I32, [P, P, P, I64, I64, P, P, F64, F64, F64, F64, F64, F64, P]),
-    "ncf_adam_flat": (I32, [P, P, P, P, I64, F64, F64, F64, F64, F64, F64, P]),
-    "ncf_adam_table_dense_grad": (I32, [P, P, P, P, I64, F64, F64, F64, F64, F64, F64, P]),
-    "ncf_fill_2d": (I32, [P, I64, I64, I64, F32, P]),
-    "ncf_adam_step_scalars": (I32, [F64, F64, F64, F64, I64, I64, P]),
-    "ncf_adam_rows_catchup": (I32, [P, P, P, P, P, P, I64, P, P, I32, I64, P, I32, P, F64, F64, F64,
-                                    F64, P]),
-    "ncf_adam_rows_apply": (I32, [P, P, P, P, P, P, P, P, I64, P, P, I32, I64, P, I32, P, F64, F64,
-                                  F64, F64, P]),
-    "ncf_adam_sweep": (I32, [P, P, P, P, P, P, I64, I64, I64, P, I32, P, F64, F64, F64, F64, P]),
-    "ncf_step_clock_advance": (I32, [P, U64, P]),
-    "ncf_adam_rows_catchup_clock": (I32, [P, P, P, P, P, P, I64, P, P, I32, I64, P, I32, P, P, F64,
-                                          F64, F64, F64, P]),
-    "ncf_adam_rows_apply_clock": (I32, [P, P, P, P, P, P, P, P, I64, P, P, I32, I64, P, I32, P, P,
-                                        F64, F64, F64, F64, P]),
-    "ncf_adam_sweep_rolling": (I32, [P, P, P, P, P, P, I64, I64, I32, I64, P, I32, P, P, F64, F64,
-                                     F64, F64, P]),
-    "ncf_adam_pairs_catchup_clock": (I32, [P, I32, I64, P, I64, I32, P, P, F64, F64, F64, F64, P]),
-    "ncf_adam_pairs_catchup_lock_clock": (I32, [P, I32, I64, P, I64, I32, I32, P, P, F64, F64, F64,
-                                                F64, P]),
-    "ncf_reduce_catchup_set_order": (I64, [I64]),
-    "ncf_reduce_batch_catchup": (I32, [P, P, I64, P, I32, I64, P, I64, I32, P, P, F64, F64, F64,
-                                       F64, P]),
-    "ncf_adam_pairs_catchup_claim_clock": (I32, [P, I32, I64, P, P, I64, I32, P, P, F64, F64, F64,
-                                                 F64, P]),
-    "ncf_adam_pairs_apply_gsum_clock": (I32, [P, I32, I64, P, I64, I32, P, P, P, I32, P, P, F64,
-                                              F64, F64, F64, P]),
-    "ncf_adam_pairs_apply_clock": (I32, [P, I32, I64, P, I64, I32, P, P, F64, F64, F64, F64, P]),
-    "ncf_adam_pairs_sweep_rolling": (I32, [P, I32, I64, I32, I32, P, P, F64, F64, F64, F64, P]),
-    "ncf_adam_pairs_sweep_rolling_part": (I32, [P, I32, I64, I32, I32, I32, I32, P, P, F64, F64, F64,
-                                                F64, P]),
-    "ncf_adam_table_bf16": (I32, [P, P, P, I64, I64, P, P, F64, F64, F64, F64, F64, F64, P]),
-    "ncf_adam_sweep_bf16": (I32, [P, P, P, P, P, P, I64, I64, I64, P, I32, P, F64, F64, F64, F64, P]),
-    "ncf_adam_flat_clock": (I32, [P, P, P, P, I64, P, I32, P, F64, F64, F64, F64, P]),
-    "ncf_adam_flat_clock_close": (I32, [P, P, P, P, I64, P, I32, P, F64, F64, F64, F64, U64, P]),
-    "ncf_score_queries": (I32, [P, I64, P, I64, I64, P, P, F32, P, P, P, P, P]),
-    "ncf_score_queries_hour": (I32, [P, P, I64, P, I64, I64, P, P, F32, P, P, P, P, P, P]),
-    "ncf_score_item_bias": (I32, [P, I64, P, P, P, P, P]),
-    "ncf_score_kth": (I32, [P, I64, I64, I32, P, I64, P, P]),
-    "ncf_score_sample_split16": (I32, [P, I64, P, I64, I64, I64, P, I64, I64, P, P]),
-    "ncf_score_kth16": (I32, [P, I64, I64, I32, P, P]),
-    "ncf_score_collect": (I32, [P, P, I64, P, P, I64, I64, P, I64, P, P, P]),
-    "ncf_score_split_items": (I32, [P, I64, I64, P, P]),
-    "ncf_score_collect_split": (I32, [P, P, I64, P, P, I64, I64, P, I64, P, P, I32, I64, P]),
-    "ncf_score_item_norm_max": (I32, [P, I64, I64, P, P]),
-    "ncf_score_margin": (I32, [P, P, I64, I64, P, F32, P, P]),
-    "ncf_score_select": (I32, [P, I64, P, P, I64, I32, P, P, P, I64, P, F32, P, P, P, P, P,
-                               P, I64, P, P, P, P]),
-    "ncf_score_merge": (I32, [P, P, I64, I64, I32, P, P, P]),
-    "ncf_rank_pair_logits": (I32, [P, I64, P, P, I64, P, P, I64, I64, P, P, P]),
-    "ncf_rank_scan": (I32, [P, I64, P, P, I64, I64, P, P, I64, P, P]),
-    "ncf_rank_seen_correct": (I32, [P, I64, P, P, P, I64, P, P, P, P, I64, I64, P, P, P]),
-    "ncf_nn_scan": (I32, [P, I64, I32, P, I64, I64, P, P, P, I64, I64, I32, P, P, P]),
-    "ncf_temporal_fwd": (I32, [P, P, P, P, I64, P, P, P, P, I64, I64, P, P, P]),
-    "ncf_temporal_bwd": (I32, [P, P, P, I64, P, I64, P, P, P, P]),
-    "ncf_hour_rows": (I32, [P, I64, P, I64, P, P, P]),
-    "ncf_hour_grad_chunk": (I64, []),
-    "ncf_hour_grad_workspace": (I64, [I64, I64]),
-    "ncf_item_scale_bwd": (I32, [P, I64, P, P, I64, I64, P, P, P, P, F32, P, F32, P, P, P, P, P]),
-    "ncf_hour_grad": (I32, [P, I64, P, I64, P, I64, I64, P, P, I64, P]),
-    "ncf_grad_clip_chunk": (I64, []),
-    "ncf_grad_clip_workspace": (I64, [P, I32]),
-    "ncf_grad_clip": (I32, [P, I32, I32, F64, P, I64, P, P]),
-}
+def _read_header(path: str = _abi.HEADER):
+    try:
+        return _abi.parse_header(path)
+    except OSError as e:
+        raise NCFLibraryError(f"cannot read {path}: the binding is generated from the header "
+                              f"beside the package ({e})") from e
 
 
+# The C-ABI is declared once, in include/ncf_hip.h; everything below is read from it (_abi.py)
+_FUNCTIONS, _STRUCTS, DEFINES = _read_header()
+
+# name -> (restype, argtypes), in header order
+SIGNATURES = _abi.signatures(_FUNCTIONS)
+
+REDUCE_LIST_MAX = DEFINES["NCF_REDUCE_LIST_MAX"]
+WGRAD_GROUP_MAX = DEFINES["NCF_WGRAD_GROUP_MAX"]
+GRAD_CLIP_MAX_SEGS = DEFINES["NCF_GRAD_CLIP_MAX_SEGS"]
+SHARD_MAX_WORLD = DEFINES["NCF_SHARD_MAX_WORLD"]
+DTYPE_F32, DTYPE_BF16 = DEFINES["NCF_DTYPE_F32"], DEFINES["NCF_DTYPE_BF16"]
+
+_MIRRORS = {}   # header struct name -> its ctypes.Structure below
+
+
+def _mirrors(name):
+    """Class decorator: the Structure's _fields_ are the header's struct `name`."""
+    def ctype(t):
+        if isinstance(t, tuple):
+            return ctype(t[0]) * t[1]
+        return _MIRRORS[t] if t in _MIRRORS else _abi.CTYPES[t]
+
+    def bind(cls):
+        cls._fields_ = [(field, ctype(t)) for field, t in _STRUCTS[name]]
+        _MIRRORS[name] = cls
+        return cls
+    return bind
+
+
+@_mirrors("ncf_reduce_desc")
 class ReduceDesc(ctypes.Structure):
     """ncf_reduce_desc (include/ncf_hip.h)."""
-    _fields_ = [("part", P), ("out", P), ("stride", I64), ("ldo", I64), ("L", ctypes.c_int32),
-                ("cols", ctypes.c_int32), ("P", ctypes.c_int32), ("accumulate", ctypes.c_int32),
-                ("scale", F32), ("reserved", ctypes.c_int32)]
 
 
-REDUCE_LIST_MAX = 64
-
-
+@_mirrors("ncf_wgrad_desc")
 class WgradDesc(ctypes.Structure):
     """ncf_wgrad_desc (include/ncf_hip.h)."""
-    _fields_ = [("dy", P), ("x", P), ("dw", P), ("dbias", P), ("ldy", I64), ("ldx", I64),
-                ("ldw", I64), ("m_out", ctypes.c_int32), ("k_in", ctypes.c_int32),
-                ("n", ctypes.c_int32), ("slabs", ctypes.c_int32), ("accumulate", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
 
 
-WGRAD_GROUP_MAX = 8
-
-
+@_mirrors("ncf_grad_seg")
 class GradSeg(ctypes.Structure):
     """ncf_grad_seg (include/ncf_hip.h)."""
-    _fields_ = [("data", P), ("rows_dev", P), ("rows", I64), ("dim", I64)]
 
 
-GRAD_CLIP_MAX_SEGS = 32
-
-
+@_mirrors("ncf_mlp_layer")
 class MlpLayer(ctypes.Structure):
     """ncf_mlp_layer (include/ncf_hip.h)."""
-    _fields_ = [("w", P), ("ldw", I64), ("b", P), ("gamma", P), ("beta", P), ("r", P), ("a", P),
-                ("mean", P), ("rstd", P), ("dlin", P), ("dbias", P), ("dgamma", P), ("dbeta", P),
-                ("dw", P)]
 
 
+@_mirrors("ncf_head_args")
 class HeadArgs(ctypes.Structure):
     """ncf_head_args (include/ncf_hip.h)."""
-    _fields_ = [(f, P) for f in ("prob", "grad_prob", "targets", "mf_pred", "mlp_pred",
-                                 "mf_user_ln", "mf_item_ln", "mlp_out_w", "final_w", "mf_out_w",
-                                 "grad_mf_user_ln", "grad_mf_item_ln", "grad_mlp_out_w",
-                                 "grad_mlp_out_b", "grad_mf_out_w", "grad_mf_out_b",
-                                 "grad_final_w", "grad_final_b", "loss")] + \
-        [("loss_denominator", ctypes.c_double), ("user_ids", P), ("group_rows", I64)]
 
 
+@_mirrors("ncf_table_pair")
 class TablePair(ctypes.Structure):
     """ncf_table_pair (include/ncf_hip.h)."""
-    _fields_ = [("p0", P), ("m0", P), ("v0", P), ("p1", P), ("m1", P), ("v1", P), ("g0", P),
-                ("g1", P), ("row_ids", P), ("stamp", P), ("rows", I64), ("param_dtype", I64)]
 
 
-DTYPE_F32, DTYPE_BF16 = 0, 1
-
-
-SHARD_MAX_WORLD = 64
-
-
+@_mirrors("ncf_shard_plan_out")
 class ShardPlanOut(ctypes.Structure):
     """ncf_shard_plan_out (include/ncf_hip.h)."""
-    _fields_ = [(f, P) for f in ("keys0", "keys1", "uniq0", "uniq1", "num_unique", "inv0", "inv1",
-                                 "counts", "send", "spos0", "spos1", "bounds", "spos64_0",
-                                 "spos64_1", "rows0", "rows1")]
 
 
+@_mirrors("ncf_shard_recv")
 class ShardRecv(ctypes.Structure):
     """ncf_shard_recv (include/ncf_hip.h): per source s, kind-0 entries at [start[s],
     start[s] + n0[s]), kind-1 entries up to start[s + 1]."""
-    _fields_ = [("world", ctypes.c_int32), ("start", ctypes.c_int32 * (SHARD_MAX_WORLD + 1)),
-                ("n0", ctypes.c_int32 * SHARD_MAX_WORLD)]
 
 
+@_mirrors("ncf_reduce_list")
 class ReduceList(ctypes.Structure):
     """ncf_reduce_list: deferred gradient reductions collected during one backward."""
-    _fields_ = [("count", ctypes.c_int32), ("reserved", ctypes.c_int32),
-                ("d", ReduceDesc * REDUCE_LIST_MAX)]
 
     @property
     def address(self) -> int:
@@ -347,7 +170,6 @@ def check_build(lib, path: str = LIB_PATH):
     sources than the ones beside this package (a stale build: _abi.py).  The sources are not
     checked when they are absent, nor for a library named by NCF_HIP_LIB (an A/B build from
     another source tree)."""
-    from . import _abi
     info = build_info(lib)
     want_abi = _abi.abi_hash(SIGNATURES)
     if info.get("abi") != want_abi:
@@ -360,7 +182,7 @@ def check_build(lib, path: str = LIB_PATH):
 
 
 # name -> CPython wrapper of the entry point (_ncffast, built beside the library by
-# build_ext.sh from SIGNATURES): the same call without ctypes' per-argument conversion
+# build_ext.sh from the header): the same call without ctypes' per-argument conversion
 FAST = {}
 
 

@@ -4,9 +4,10 @@ libncf_hip.so with one PyArg_ParseTuple per call instead of ctypes' per-argument
 
 ctypes stays the loader (``_lib.load()`` resolves every symbol and checks the signatures); the
 extension receives the resolved function addresses once (``bind(index, address)``) and then
-only forwards arguments.  One wrapper per signature of ``_lib.SIGNATURES`` whose result is an
-integer; the argument kinds map to format units: pointer -> ``O&`` (None -> NULL, or an int
-address), int64 -> ``L``, int32 -> ``i``, uint64 -> ``K``, float -> ``f``, double -> ``d``.
+only forwards arguments.  One wrapper per entry point of include/ncf_hip.h
+(``_abi.parse_header``) whose result is an integer; the argument kinds map to format units:
+pointer -> ``O&`` (None -> NULL, or an int address), int64 -> ``L``, int32 -> ``i``, uint64 ->
+``K``, float -> ``f``, double -> ``d``.
 Measured reason (tools/dropin_host.py): a 25-argument ctypes call costs ~7 us of host time, and
 a training step makes ~13 of them on the reference call pattern's critical host path.
 
@@ -23,21 +24,26 @@ passed for that slot.
 
     python gen_fastcall.py OUT.c
 """
-import ctypes
+import importlib.util
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def load_signatures():
-    """Read SIGNATURES from _lib.py without importing torch (exec of the table only)."""
-    src = open(os.path.join(HERE, "..", "_lib.py")).read()
-    start = src.index("P = ctypes.c_void_p")
-    end = src.index("\nclass ReduceDesc")
-    ns = {"ctypes": ctypes}
-    exec(src[start:end], ns)     # the type aliases + the SIGNATURES literal
-    return ns["SIGNATURES"], ns
+def load_abi():
+    """_abi.py by file path (no package import, so no torch)."""
+    spec = importlib.util.spec_from_file_location("_abi", os.path.join(HERE, "..", "_abi.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+# _abi type code -> (format unit, C type, converter)
+KINDS = {"p": ("O&", "void*", "ncf_ptr_conv"), "l": ("L", "long long", None),
+         "i": ("i", "int", None), "f": ("f", "float", None), "d": ("d", "double", None),
+         "u": ("K", "unsigned long long", None)}
+RETS = {"i": ("int", "PyLong_FromLong"), "l": ("long long", "PyLong_FromLongLong")}
 
 
 TAPE_RUNTIME = r"""
@@ -238,16 +244,8 @@ static PyObject* py_tape_replay(PyObject* self, PyObject* a) {
 
 
 def main(out):
-    sigs, ns = load_signatures()
-    kinds = {id(ns["P"]): ("O&", "void*", "ncf_ptr_conv"),
-             id(ns["I64"]): ("L", "long long", None),
-             id(ns["I32"]): ("i", "int", None),
-             id(ctypes.c_int32): ("i", "int", None),
-             id(ns["F32"]): ("f", "float", None),
-             id(ns["F64"]): ("d", "double", None),
-             id(ns["U64"]): ("K", "unsigned long long", None)}
-    rets = {id(ns["I32"]): ("int", "PyLong_FromLong"), id(ns["I64"]): ("long long", "PyLong_FromLongLong")}
-    lines = ["/* generated by gen_fastcall.py from _lib.SIGNATURES -- do not edit */",
+    sigs = load_abi().parse_header()[0]
+    lines = ["/* generated by gen_fastcall.py from include/ncf_hip.h -- do not edit */",
              "#define PY_SSIZE_T_CLEAN", "#include <Python.h>", "",
              "static int ncf_ptr_conv(PyObject* o, void** out) {",
              "  if (o == Py_None) { *out = NULL; return 1; }",
@@ -257,18 +255,18 @@ def main(out):
              TAPE_RUNTIME]
     names = []
     for name, (res, args) in sigs.items():
-        if id(res) not in rets or any(id(a) not in kinds for a in args):
+        if res not in RETS or any(a not in KINDS for a in args):
             continue
-        rtype, rconv = rets[id(res)]
+        rtype, rconv = RETS[res]
         idx = len(names)
         names.append(name)
-        fmt = "".join(kinds[id(a)][0] for a in args)
-        decl = ", ".join(kinds[id(a)][1] for a in args) or "void"
+        fmt = "".join(KINDS[a][0] for a in args)
+        decl = ", ".join(KINDS[a][1] for a in args) or "void"
         lines.append(f"typedef {rtype} (*fn_{idx})({decl});")
         lines.append(f"static fn_{idx} p_{idx} = NULL;")
-        fields = " ".join(f"{kinds[id(t)][1]} a{j};" for j, t in enumerate(args)) or "char unused;"
+        fields = " ".join(f"{KINDS[t][1]} a{j};" for j, t in enumerate(args)) or "char unused;"
         lines.append(f"typedef struct {{ {fields} }} A_{idx};")
-        offs = [f"(int)offsetof(A_{idx}, a{j})" for j, t in enumerate(args) if kinds[id(t)][2]]
+        offs = [f"(int)offsetof(A_{idx}, a{j})" for j, t in enumerate(args) if KINDS[t][2]]
         lines.append(f"static const int po_{idx}[] = {{" + ", ".join(offs + ["-1"]) + "};")
         aoffs = [f"(int)offsetof(A_{idx}, a{j})" for j in range(len(args))] or ["0"]
         awids = [f"(int)sizeof(((A_{idx}*)0)->a{j})" for j in range(len(args))] or ["0"]
@@ -276,11 +274,11 @@ def main(out):
         lines.append(f"static const int aw_{idx}[] = {{" + ", ".join(awids) + "};")
         lines.append(f"static PyObject* w_{idx}(PyObject* self, PyObject* a) {{  /* {name} */")
         for j, t in enumerate(args):
-            lines.append(f"  {kinds[id(t)][1]} a{j} = 0;")
+            lines.append(f"  {KINDS[t][1]} a{j} = 0;")
         refs = []
         for j, t in enumerate(args):
-            if kinds[id(t)][2]:
-                refs.append(f"{kinds[id(t)][2]}, &a{j}")
+            if KINDS[t][2]:
+                refs.append(f"{KINDS[t][2]}, &a{j}")
             else:
                 refs.append(f"&a{j}")
         argsref = (", " + ", ".join(refs)) if refs else ""

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void k_kth(const float* __restrict__ logits, i
 // it is below the exact K-th by less than (max - min) / 65536, far inside the margin).  Linear
 // bins spread the logits over many bins (the exponent byte of the radix keys puts nearly all of
 // them in one or two, and their LDS atomics serialise).  For S <= kKthLdsMax.
-constexpr int64_t kKthLdsMax = 38912;   // 152 KB of logits (of the 160 KB of LDS)
+constexpr int64_t kKthLdsMax = NCF_SCORE_KTH_LDS_MAX;   // 152 KB of logits (of the 160 KB of LDS)
 
 // wave 0: the highest bin d with (count of bins >= d) >= need; returns d, and the count above d
 // in *above (lane l holds bins 4l..4l+3)
@@ -899,7 +899,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2))) vo
 }
 
 // ---- 4. per-user selection: bitonic sort (descending) of 64-bit keys (logit key | ~item)
-constexpr int kSelectMax = 8192;   // (bitonic_desc: select_dev.h)
+constexpr int kSelectMax = NCF_SCORE_SELECT_MAX;   // (bitonic_desc: select_dev.h)
 
 // Per user: the K best candidates without sorting the whole list.  The candidates' order keys
 // (fkey of the logit) go to LDS; a radix select over key - min (8-bit digits from the highest bit

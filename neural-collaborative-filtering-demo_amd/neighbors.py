@@ -31,7 +31,7 @@ DIMS = (16, 32, 64, 128)
 QUERY_BLOCK = 32       # queries per workgroup (the MFMA's 32 rows)
 NUM_CUS = 256
 MIN_SLAB = 1024
-MERGE_MAX = 8192       # ncf_score_merge's longest candidate list
+MERGE_MAX = _lib.DEFINES["NCF_SCORE_SELECT_MAX"]   # ncf_score_merge's longest candidate list
 
 Plan = namedtuple("Plan", "slab_items n_slabs g1 g2")
 Plan.__doc__ = """``n_slabs`` slabs of ``slab_items`` items cover the catalogue (the last one may be

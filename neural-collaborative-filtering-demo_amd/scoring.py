@@ -446,8 +446,9 @@ SORT_USERS = False
 # the split scan's item split raised from the expected candidates per user (the launch's
 # expected_per_user: fewer per-wave LDS slice overflows; tested invisible in the results)
 SIZED_SPLIT = True
-KTH_LDS_MAX = 38912   # = score.hip kKthLdsMax
-SELECT_MAX = 8192     # = score.hip kSelectMax: the longest candidate list the select takes
+KTH_LDS_MAX = _lib.DEFINES["NCF_SCORE_KTH_LDS_MAX"]   # score.hip kKthLdsMax
+# score.hip kSelectMax: the longest candidate list the select takes
+SELECT_MAX = _lib.DEFINES["NCF_SCORE_SELECT_MAX"]
 # the threshold sample on bf16 matrix cores, fp16 logits rounded down (ncf_score_sample_split16 +
 # ncf_score_kth16, its k-th lowered by the two-term bound) instead of the fp32 sample GEMM +
 # fp32 k-th (measured, 10K x 1M eager: top-100 4.25 -> 3.73 ms, top-10 2.78 -> 2.70); needs the

