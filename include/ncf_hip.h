@@ -1041,16 +1041,38 @@ int ncf_adam_sweep_rolling(float* p0, float* m0, float* v0, float* p1, float* m1
  * tables (sharing the row index), their moments, compact gradients (apply), the step's unique
  * rows and the stamps; count[k] = unique rows of kind k (ncf_dedup_ids).                      */
 /* param_dtype: NCF_DTYPE_F32, or NCF_DTYPE_BF16 when p0 / p1 point at bf16 rows (the moments stay
- * fp32; the parameter is rounded to bf16, nearest even, after every step it takes).           */
+ * fp32; the parameter is rounded to bf16, nearest even, after every step it takes).
+ * NCF_DTYPE_BF16_SR: bf16 rows rounded stochastically under round_seed (the low 32 bits count;
+ * the same in every pair of a call).  The store of step s on element e = row * dim + col of
+ * table j (0: p0, 1: p1) of pair kind (0: users, 1: items) draws 16 uniform bits
+ *   r = bits(round_seed, kind, j, s, e)
+ *     = (mix32((uint32)e * 0x9E3779B9
+ *              ^ mix32(mix32(round_seed ^ 0x9E3779B9 * (2 * (e >> 32) + kind + 1)) + s))
+ *        >> 16 * j) & 0xFFFF          (mix32: x ^= x >> 16, x *= 0x7FEB352D, x ^= x >> 15,
+ *                                      x *= 0x846CA68B, x ^= x >> 16; everything modulo 2^32)
+ * and stores (bits_of(x) + r) >> 16 for the fp32 result x of the step: a value bf16 holds is
+ * stored unchanged, any other has its magnitude rounded up with probability low16(x) / 65536 and
+ * down otherwise, so the expectation of the stored value is x.  Inf stays inf and NaN stays NaN,
+ * as under nearest even.  bits is a pure function of its five arguments: the stored value does
+ * not depend on the launch geometry, on which entry point takes the step, or on when a deferred
+ * zero-gradient step is replayed; a replay rounds after every owed step, each with its own bits.
+ * Entry points taking ncf_table_pair implement it, except ncf_adam_pairs_apply_gsum_clock, which
+ * returns NCF_ERR_ARG for it, as every one does for a param_dtype it does not know.
+ * ncf_adam_table_bf16 / ncf_adam_sweep_bf16 take no seed and round to nearest even.
+ * (FBGEMM's table-batched embeddings, the reference's sharded backend under torchrec, round
+ * low-precision weights stochastically; src/model/trainer.py:285's fp32 Adam.step has no
+ * rounding at all, which the expectation reproduces.)                                         */
 #define NCF_DTYPE_F32 0
 #define NCF_DTYPE_BF16 1
+#define NCF_DTYPE_BF16_SR 2
 typedef struct ncf_table_pair {
   float *p0, *m0, *v0, *p1, *m1, *v1;
   const float *g0, *g1;
   const int64_t* row_ids;
   int32_t* stamp;
   int64_t rows;
-  int64_t param_dtype;
+  int32_t param_dtype;
+  int32_t round_seed;
 } ncf_table_pair;
 /* The reduce with the deferred table Adam's apply of the step fused in (FusedTrainStep): each
  * unique row's two gradient rows, once complete (in the reduce for a segment of one piece, in

@@ -58,6 +58,7 @@ WGRAD_GROUP_MAX = DEFINES["NCF_WGRAD_GROUP_MAX"]
 GRAD_CLIP_MAX_SEGS = DEFINES["NCF_GRAD_CLIP_MAX_SEGS"]
 SHARD_MAX_WORLD = DEFINES["NCF_SHARD_MAX_WORLD"]
 DTYPE_F32, DTYPE_BF16 = DEFINES["NCF_DTYPE_F32"], DEFINES["NCF_DTYPE_BF16"]
+DTYPE_BF16_SR = DEFINES["NCF_DTYPE_BF16_SR"]     # bf16 rows, rounded stochastically
 
 _MIRRORS = {}   # header struct name -> its ctypes.Structure below
 

@@ -209,13 +209,13 @@ __global__ __launch_bounds__(256) void k_adam_flat_clock(float* __restrict__ p,
 
 // ---- both id kinds per launch (blockIdx.y = kind; PairArgs and the catch-up's body:
 // adam_catchup_dev.h)
-template <int D, bool BF = false>
+template <int D, bool BF = false, bool SR = false>
 __global__ __launch_bounds__(256) void k_pairs_catchup(const PairArgs a, const uint32_t* __restrict__ count,
                                                        int64_t max_n, int32_t target_rel,
                                                        const ncf_step_clock* __restrict__ clock,
                                                        const float* __restrict__ table,
                                                        AdamScalars s, int lock) {
-  pairs_catchup_body<D, BF>(a, blockIdx.y, blockIdx.x, count, max_n, target_rel, clock, table, s,
+  pairs_catchup_body<D, BF, SR>(a, blockIdx.y, blockIdx.x, count, max_n, target_rel, clock, table, s,
                             lock);
 }
 
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void k_pairs_catchup(const PairArgs a, const u
 // backward needs can run on another stream beside the forward.  Locked rows (stamp = t |
 // NCF_STAMP_LOCK) compare above any target and are left alone.  Out-of-range ids are skipped
 // (the gather flags them).
-template <int D, bool BF = false>
+template <int D, bool BF = false, bool SR = false>
 __global__ __launch_bounds__(256) void k_pairs_catchup_claim(const PairArgs a,
                                                              const int64_t* __restrict__ ids0,
                                                              const int64_t* __restrict__ ids1,
@@ -246,10 +246,10 @@ __global__ __launch_bounds__(256) void k_pairs_catchup_claim(const PairArgs a,
   int32_t from = target;
   if (sub == 0) from = atomicMax(&a.stamp[k][row], target);
   from = __shfl(from, (int)(threadIdx.x & 63) - sub, 64);   // the claim of this row's lane group
-  catch_up_row<D, BF>(a.t[k], row, sub, from, target, table, s);
+  catch_up_row<D, BF, SR>(a.t[k], row, sub, from, target, table, s, a.seed, k);
 }
 
-template <int D, bool BF = false>
+template <int D, bool BF = false, bool SR = false>
 __global__ __launch_bounds__(256) void k_pairs_apply(const PairArgs a, const uint32_t* __restrict__ count,
                                                      int64_t max_n, int32_t step_rel,
                                                      const ncf_step_clock* __restrict__ clock,
@@ -277,6 +277,11 @@ __global__ __launch_bounds__(256) void k_pairs_apply(const PairArgs a, const uin
   }
   adam4(p0, m0, v0, g0, ns, bc, s);
   if (two) adam4(p1, m1, v1, g1, ns, bc, s);
+  if (SR) {   // this step's bits of the row's elements (ncf_sr_*): exact in bf16 afterwards
+    const uint32_t key = ncf_sr_key(ncf_sr_base(a.seed, k, (uint32_t)((uint64_t)o >> 32)), step);
+    p0 = ncf_sr_round4<0>(p0, key, (uint32_t)o);
+    if (two) p1 = ncf_sr_round4<1>(p1, key, (uint32_t)o);
+  }
   stp4<BF>(t.p0, o, p0); st4(t.m0 + o, m0); st4(t.v0 + o, v0);
   if (two) { stp4<BF>(t.p1, o, p1); st4(t.m1 + o, m1); st4(t.v1 + o, v1); }
   if (sub == 0) a.stamp[k][row] = step;
@@ -326,7 +331,7 @@ __global__ __launch_bounds__(256) void k_pairs_apply_gsum(const PairArgs a, cons
 }
 
 // part `part` of `nparts` (consecutive row ranges) of the slice of step clock->t + step_rel
-template <int D, bool BF = false>
+template <int D, bool BF = false, bool SR = false>
 __global__ __launch_bounds__(256) void k_pairs_sweep(const PairArgs a, int32_t every,
                                                      int32_t step_rel,
                                                      const ncf_step_clock* __restrict__ clock,
@@ -348,7 +353,7 @@ __global__ __launch_bounds__(256) void k_pairs_sweep(const PairArgs a, int32_t e
     const int64_t row = row0 + e / L;
     const int sub = (int)(e % L);
     const int32_t from = stamp[row];
-    catch_up_row<D, BF>(a.t[k], row, sub, from, target, table, s);
+    catch_up_row<D, BF, SR>(a.t[k], row, sub, from, target, table, s, a.seed, k);
     if (sub == 0 && from < target) stamp[row] = target;
   }
 }
@@ -527,7 +532,9 @@ template <int D>
 int pairs_catchup_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, int32_t rel,
                     const ncf_step_clock* clock, const float* table, AdamScalars s,
                     hipStream_t st, int lock = 0) {
-  if (a.bf)
+  if (a.sr)
+    hipLaunchKernelGGL((k_pairs_catchup<D, true, true>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
+  else if (a.bf)
     hipLaunchKernelGGL((k_pairs_catchup<D, true>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
   else
     hipLaunchKernelGGL((k_pairs_catchup<D, false>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
@@ -538,7 +545,9 @@ int pairs_catchup_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, int
 template <int D>
 int pairs_apply_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, int32_t rel,
                   const ncf_step_clock* clock, const float* table, AdamScalars s, hipStream_t st) {
-  if (a.bf)
+  if (a.sr)
+    hipLaunchKernelGGL((k_pairs_apply<D, true, true>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
+  else if (a.bf)
     hipLaunchKernelGGL((k_pairs_apply<D, true>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
   else
     hipLaunchKernelGGL((k_pairs_apply<D, false>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
@@ -572,7 +581,9 @@ int pairs_sweep_d(PairArgs a, int n, int32_t every, int32_t rel, const ncf_step_
   for (int k = 0; k < n; ++k) slice = max(slice, (a.rows[k] + every - 1) / every);
   slice = (slice + nparts - 1) / nparts;
   const int gx = (int)min((int64_t)grid_for(slice * Replay<D>::LPR), 256 * g_sweep_blocks_per_cu);
-  if (a.bf)
+  if (a.sr)
+    hipLaunchKernelGGL((k_pairs_sweep<D, true, true>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
+  else if (a.bf)
     hipLaunchKernelGGL((k_pairs_sweep<D, true>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
   else
     hipLaunchKernelGGL((k_pairs_sweep<D, false>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
@@ -770,6 +781,7 @@ extern "C" int ncf_adam_pairs_catchup_clock(const ncf_table_pair* pairs, int npa
                                             double eps, double weight_decay, void* stream) {
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table,
                 "ncf_adam_pairs_catchup_clock: bad args");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_catchup_clock: param_dtype");
   if (max_n <= 0) return NCF_OK;
   NCF_DISPATCH_DIM(dim, pairs_catchup_d, pair_args(pairs, npairs), npairs, count, max_n,
                    target_rel, clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
@@ -791,6 +803,7 @@ extern "C" int ncf_adam_pairs_catchup_lock_clock(const ncf_table_pair* pairs, in
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table &&
                     (lock == 0 || lock == 1),
                 "ncf_adam_pairs_catchup_lock_clock: bad args");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_catchup_lock_clock: param_dtype");
   if (max_n <= 0) return NCF_OK;
   NCF_DISPATCH_DIM(dim, pairs_catchup_d, pair_args(pairs, npairs), npairs, count, max_n,
                    target_rel, clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
@@ -802,7 +815,10 @@ int pairs_claim_d(PairArgs a, int npairs, const int64_t* ids0, const int64_t* id
                   int32_t rel, const ncf_step_clock* clock, const float* table, AdamScalars s,
                   hipStream_t st) {
   const dim3 grid((unsigned)ncf_cdiv(n * Replay<D>::LPR, 256), npairs);
-  if (a.bf)
+  if (a.sr)
+    hipLaunchKernelGGL((k_pairs_catchup_claim<D, true, true>), grid, dim3(256), 0, st, a, ids0, ids1, n,
+                       rel, clock, table, s);
+  else if (a.bf)
     hipLaunchKernelGGL((k_pairs_catchup_claim<D, true>), grid, dim3(256), 0, st, a, ids0, ids1, n,
                        rel, clock, table, s);
   else
@@ -824,6 +840,7 @@ extern "C" int ncf_adam_pairs_catchup_claim_clock(const ncf_table_pair* pairs, i
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && ids0 && (npairs < 2 || ids1) && clock &&
                     step_table && n >= 0,
                 "ncf_adam_pairs_catchup_claim_clock: bad args");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_catchup_claim_clock: param_dtype");
   if (n == 0) return NCF_OK;
   NCF_DISPATCH_DIM(dim, pairs_claim_d, pair_args(pairs, npairs), npairs, ids0, ids1, n,
                    target_rel, clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
@@ -837,6 +854,7 @@ extern "C" int ncf_adam_pairs_apply_clock(const ncf_table_pair* pairs, int npair
                                           double weight_decay, void* stream) {
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table,
                 "ncf_adam_pairs_apply_clock: bad args");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_apply_clock: param_dtype");
   for (int k = 0; k < npairs; ++k)
     NCF_CHECK_ARG(pairs[k].g0 && (!pairs[k].p1 || pairs[k].g1), "ncf_adam_pairs_apply_clock: gradients");
   if (max_n <= 0) return NCF_OK;
@@ -857,6 +875,8 @@ extern "C" int ncf_adam_pairs_apply_gsum_clock(const ncf_table_pair* pairs, int 
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table && got &&
                     pos0 && pos1 && world >= 1,
                 "ncf_adam_pairs_apply_gsum_clock: bad args");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs) && pairs[0].param_dtype != NCF_DTYPE_BF16_SR,
+                "ncf_adam_pairs_apply_gsum_clock: param_dtype (no stochastic rounding here)");
   for (int k = 0; k < npairs; ++k)
     NCF_CHECK_ARG(pairs[k].p1, "ncf_adam_pairs_apply_gsum_clock: both tables of a pair");
   if (max_n <= 0) return NCF_OK;
@@ -872,6 +892,7 @@ extern "C" int ncf_adam_pairs_sweep_rolling(const ncf_table_pair* pairs, int npa
                                             double weight_decay, void* stream) {
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && clock && step_table && sweep_every >= 1,
                 "ncf_adam_pairs_sweep_rolling: bad args");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_sweep_rolling: param_dtype");
   NCF_DISPATCH_DIM(dim, pairs_sweep_d, pair_args(pairs, npairs), npairs, sweep_every, step_rel,
                    clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
                    (hipStream_t)stream);
@@ -889,6 +910,7 @@ extern "C" int ncf_adam_pairs_sweep_rolling_part(const ncf_table_pair* pairs, in
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && clock && step_table && sweep_every >= 1 &&
                     nparts >= 1 && part >= 0 && part < nparts,
                 "ncf_adam_pairs_sweep_rolling_part: bad args");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_sweep_rolling_part: param_dtype");
   NCF_DISPATCH_DIM(dim, pairs_sweep_d, pair_args(pairs, npairs), npairs, sweep_every, step_rel,
                    clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
                    (hipStream_t)stream, part, nparts);

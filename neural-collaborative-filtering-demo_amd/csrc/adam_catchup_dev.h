@@ -40,13 +40,20 @@ struct Replay {
 // scalar-load latency hides behind 8 steps of VALU work instead of stalling every step (the
 // step table is padded >= 4096 steps past any target, deferred.py _ensure).  Same adam1 calls in
 // the same order: results are bit-identical to the step-by-step loop.
-template <int EPL, bool PAIR, bool BF = false>
+// SR (with BF): the parameter is rounded stochastically after every step, each step with its
+// own bits (ncf_sr_*, ncf_common.h): sr_base is the row's ncf_sr_base, wave-uniform like the
+// bounds, so a step's key is scalar work; e_lo the low word of the lane's first element.
+template <int EPL, bool PAIR, bool BF = false, bool SR = false>
 __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, float* p1,
                                                float* m1, float* v1, int32_t from, int32_t to,
                                                const float* __restrict__ table,
-                                               const AdamScalars& s) {
+                                               const AdamScalars& s, uint32_t sr_base = 0,
+                                               uint32_t e_lo = 0) {
   constexpr int C = 8;                 // steps per chunk
   int32_t q = from + 1;
+  uint32_t ew[EPL];                    // SR: the elements' words, the same at every step
+#pragma unroll
+  for (int j = 0; j < EPL; ++j) ew[j] = SR ? ncf_sr_elem(e_lo + j * 64) : 0u;
   float sc[2 * C];
 #pragma unroll
   for (int k = 0; k < C; ++k) {
@@ -63,12 +70,18 @@ __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, 
     __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ahead of this chunk's steps
 #pragma unroll
     for (int k = 0; k < C; ++k) {
+      const uint32_t key = SR ? ncf_sr_key(sr_base, q + k) : 0u;
 #pragma unroll
       for (int j = 0; j < EPL; ++j) {
         adam0(p0[j], m0[j], v0[j], sc[2 * k], sc[2 * k + 1], s);
-        if (BF) p0[j] = ncf_round_bf16(p0[j]);   // bf16 tables: stored (rounded) every step
+        if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);   // bf16 tables: stored (rounded) every step
         if (PAIR) adam0(p1[j], m1[j], v1[j], sc[2 * k], sc[2 * k + 1], s);
-        if (PAIR && BF) p1[j] = ncf_round_bf16(p1[j]);
+        if (PAIR && BF && !SR) p1[j] = ncf_round_bf16(p1[j]);
+        if (SR) {
+          const uint32_t h = ncf_sr_bits(key, ew[j]);
+          p0[j] = ncf_sr_round0(p0[j], h);
+          if (PAIR) p1[j] = ncf_sr_round1(p1[j], h);
+        }
       }
     }
 #pragma unroll
@@ -78,20 +91,29 @@ __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, 
 #pragma unroll
   for (int k = 0; k < C - 1; ++k) {    // the last to - q + 1 < C steps
     if (q + k > to) break;
+    const uint32_t key = SR ? ncf_sr_key(sr_base, q + k) : 0u;
 #pragma unroll
     for (int j = 0; j < EPL; ++j) {
       adam0(p0[j], m0[j], v0[j], sc[2 * k], sc[2 * k + 1], s);
-      if (BF) p0[j] = ncf_round_bf16(p0[j]);
+      if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);
       if (PAIR) adam0(p1[j], m1[j], v1[j], sc[2 * k], sc[2 * k + 1], s);
-      if (PAIR && BF) p1[j] = ncf_round_bf16(p1[j]);
+      if (PAIR && BF && !SR) p1[j] = ncf_round_bf16(p1[j]);
+      if (SR) {
+        const uint32_t h = ncf_sr_bits(key, ew[j]);
+        p0[j] = ncf_sr_round0(p0[j], h);
+        if (PAIR) p1[j] = ncf_sr_round1(p1[j], h);
+      }
     }
   }
 }
 
-template <int D, bool BF = false>
+// SR: stochastic rounding under `seed` for the tables of pair `kind` (ncf_sr_*)
+template <int D, bool BF = false, bool SR = false>
 __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, int sub, int32_t from,
                                              int32_t to, const float* __restrict__ table,
-                                             const AdamScalars& s) {
+                                             const AdamScalars& s, uint32_t seed = 0,
+                                             int kind = 0) {
+  static_assert(BF || !SR, "stochastic rounding is a store of bf16 rows");
   constexpr int EPL = Replay<D>::EPL, LPR = Replay<D>::LPR;
   if (Replay<D>::LPR == 64) {   // the whole wave holds this row: make the bounds scalar
     from = __builtin_amdgcn_readfirstlane(from);
@@ -99,6 +121,12 @@ __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, in
   }
   if (from >= to) return;
   const int64_t o = row * D + sub;
+  const uint32_t e_lo = (uint32_t)o;
+  uint32_t base = 0;
+  if (SR) {
+    base = ncf_sr_base(seed, kind, (uint32_t)((uint64_t)o >> 32));
+    if (Replay<D>::LPR == 64) base = __builtin_amdgcn_readfirstlane(base);
+  }
   float p0[EPL], m0[EPL], v0[EPL], p1[EPL], m1[EPL], v1[EPL];
 #pragma unroll
   for (int j = 0; j < EPL; ++j) {
@@ -110,16 +138,22 @@ __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, in
       p1[j] = ldp<BF>(t.p1, o + j * LPR); m1[j] = t.m1[o + j * LPR]; v1[j] = t.v1[o + j * LPR];
     }
     if (Replay<D>::LPR == 64) {
-      replay_uniform<EPL, true, BF>(p0, m0, v0, p1, m1, v1, from, to, table, s);
+      replay_uniform<EPL, true, BF, SR>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
     } else {
 #pragma unroll 2
       for (int32_t q = from + 1; q <= to; ++q) {
         const float ra = table[4 * q + 2], rb = table[4 * q + 3];
+        const uint32_t key = SR ? ncf_sr_key(base, q) : 0u;
 #pragma unroll
         for (int j = 0; j < EPL; ++j) {
           adam0(p0[j], m0[j], v0[j], ra, rb, s);
           adam0(p1[j], m1[j], v1[j], ra, rb, s);
-          if (BF) { p0[j] = ncf_round_bf16(p0[j]); p1[j] = ncf_round_bf16(p1[j]); }
+          if (BF && !SR) { p0[j] = ncf_round_bf16(p0[j]); p1[j] = ncf_round_bf16(p1[j]); }
+          if (SR) {
+            const uint32_t h = ncf_sr_bits(key, ncf_sr_elem(e_lo + j * LPR));
+            p0[j] = ncf_sr_round0(p0[j], h);
+            p1[j] = ncf_sr_round1(p1[j], h);
+          }
         }
       }
     }
@@ -128,15 +162,17 @@ __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, in
       stp<BF>(t.p1, o + j * LPR, p1[j]); t.m1[o + j * LPR] = m1[j]; t.v1[o + j * LPR] = v1[j];
     }
   } else if (Replay<D>::LPR == 64) {
-    replay_uniform<EPL, false, BF>(p0, m0, v0, p1, m1, v1, from, to, table, s);
+    replay_uniform<EPL, false, BF, SR>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
   } else {
 #pragma unroll 2
     for (int32_t q = from + 1; q <= to; ++q) {
       const float ra = table[4 * q + 2], rb = table[4 * q + 3];
+      const uint32_t key = SR ? ncf_sr_key(base, q) : 0u;
 #pragma unroll
       for (int j = 0; j < EPL; ++j) {
         adam0(p0[j], m0[j], v0[j], ra, rb, s);
-        if (BF) p0[j] = ncf_round_bf16(p0[j]);
+        if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);
+        if (SR) p0[j] = ncf_sr_round0(p0[j], ncf_sr_bits(key, ncf_sr_elem(e_lo + j * LPR)));
       }
     }
   }
@@ -153,7 +189,17 @@ struct PairArgs {
   int32_t* stamp[2];
   int64_t rows[2];
   int bf;            // parameter rows are bf16 (host-side dispatch only)
+  int sr;            // ... and rounded stochastically (NCF_DTYPE_BF16_SR; host-side dispatch)
+  uint32_t seed;     // round_seed of the stochastic rounding (ncf_sr_base)
 };
+
+// whether the n pairs name one parameter dtype this build knows (NCF_DTYPE_*)
+inline bool pair_dtypes_ok(const ncf_table_pair* p, int n) {
+  for (int k = 0; k < n && k < 2; ++k)
+    if (p[k].param_dtype != p[0].param_dtype || p[k].round_seed != p[0].round_seed) return false;
+  return p[0].param_dtype == NCF_DTYPE_F32 || p[0].param_dtype == NCF_DTYPE_BF16 ||
+         p[0].param_dtype == NCF_DTYPE_BF16_SR;
+}
 
 inline PairArgs pair_args(const ncf_table_pair* p, int n) {
   PairArgs a;
@@ -164,13 +210,15 @@ inline PairArgs pair_args(const ncf_table_pair* p, int n) {
     a.stamp[k] = p[k].stamp;
     a.rows[k] = p[k].rows;
   }
-  a.bf = p[0].param_dtype == NCF_DTYPE_BF16;
+  a.sr = p[0].param_dtype == NCF_DTYPE_BF16_SR;
+  a.bf = a.sr || p[0].param_dtype == NCF_DTYPE_BF16;
+  a.seed = (uint32_t)p[0].round_seed;
   return a;
 }
 
 // Block bx (of ncf_cdiv(max_n * Replay<D>::LPR, 256), 256 threads) of the catch-up of kind k's
 // listed rows ids[k][0 .. count[k]) to clock->t + target_rel.
-template <int D, bool BF>
+template <int D, bool BF, bool SR = false>
 __device__ __forceinline__ void pairs_catchup_body(const PairArgs& a, int k, uint32_t bx,
                                                    const uint32_t* __restrict__ count,
                                                    int64_t max_n, int32_t target_rel,
@@ -186,7 +234,7 @@ __device__ __forceinline__ void pairs_catchup_body(const PairArgs& a, int k, uin
   const int64_t row = a.ids[k][c];
   int32_t* stamp = a.stamp[k];
   const int32_t from = stamp[row];
-  catch_up_row<D, BF>(a.t[k], row, sub, from, target, table, s);
+  catch_up_row<D, BF, SR>(a.t[k], row, sub, from, target, table, s, a.seed, k);
   // lock: every listed row is marked in flight (current through target, its gradient step still
   // to come: the step's apply writes the plain stamp back); replays of other rows skip it.  A
   // listed row that is locked already, or ahead of the target, keeps its stamp: it was not

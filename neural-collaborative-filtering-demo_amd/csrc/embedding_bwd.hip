@@ -430,11 +430,15 @@ extern "C" int ncf_embedding_bwd_reduce_apply_clock(
     const float* step_table, double beta1, double beta2, double eps_adam, double weight_decay,
     void* stream) {
   NCF_CHECK_ARG(pairs && clock && step_table, "ncf_embedding_bwd_reduce_apply_clock: bad args");
+  NCF_CHECK_ARG(pairs[0].param_dtype == NCF_DTYPE_F32 || pairs[0].param_dtype == NCF_DTYPE_BF16 ||
+                    pairs[0].param_dtype == NCF_DTYPE_BF16_SR,
+                "ncf_embedding_bwd_reduce_apply_clock: param_dtype");
   ApplyArgs ap{};
   for (int k = 0; k < 2; ++k) {
     NCF_CHECK_ARG(pairs[k].p0 && pairs[k].m0 && pairs[k].v0 && pairs[k].p1 && pairs[k].m1 &&
                       pairs[k].v1 && pairs[k].stamp &&
-                      pairs[k].param_dtype == pairs[0].param_dtype,
+                      pairs[k].param_dtype == pairs[0].param_dtype &&
+                      pairs[k].round_seed == pairs[0].round_seed,
                   "ncf_embedding_bwd_reduce_apply_clock: incomplete table pair");
     ap.p[k][0] = pairs[k].p0; ap.m[k][0] = pairs[k].m0; ap.v[k][0] = pairs[k].v0;
     ap.p[k][1] = pairs[k].p1; ap.m[k][1] = pairs[k].m1; ap.v[k][1] = pairs[k].v1;
@@ -445,6 +449,27 @@ extern "C" int ncf_embedding_bwd_reduce_apply_clock(
   ap.s = ncf_adam::consts_of(beta1, beta2, eps_adam, weight_decay);
   ap.step_rel = step_rel;
   ap.on = 1;
+  if (pairs[0].param_dtype == NCF_DTYPE_BF16_SR) {
+    // Stochastic rounding: the reduce as ncf_embedding_bwd_reduce_bf16 runs it, then the apply
+    // as its own launch (ncf_adam_pairs_apply_clock over this call's unique rows and compact
+    // gradients; totals[k] of the workspace is num_unique[k]).  Not inside the reduce: a third
+    // instantiation of k_piece_reduce_ln did not reproduce the LayerNorm backward of the other
+    // two bit for bit (measured: moments one fp32 ulp off on 15 % of the touched elements;
+    // supposed cause: its plain multiply-adds contracted differently), and every schedule of
+    // a step has to store the same bits.
+    const int rc = embedding_bwd_reduce(
+        true, n, dim, num_users, num_items, dy_mf_user, dy_mlp_user, dy_mf_item, dy_mlp_item,
+        pairs[0].p0, pairs[0].p1, pairs[1].p0, pairs[1].p1, mf_gamma, mlp_gamma, eps, grad_mf_user,
+        grad_mlp_user, grad_mf_item, grad_mlp_item, uniq_users, uniq_items, grad_mf_gamma,
+        grad_mf_beta, grad_mlp_gamma, grad_mlp_beta, workspace, workspace_bytes, defer, stream);
+    if (rc != NCF_OK || n == 0) return rc;
+    ncf_table_pair pr[2] = {pairs[0], pairs[1]};
+    pr[0].g0 = grad_mf_user; pr[0].g1 = grad_mlp_user; pr[0].row_ids = uniq_users;
+    pr[1].g0 = grad_mf_item; pr[1].g1 = grad_mlp_item; pr[1].row_ids = uniq_items;
+    return ncf_adam_pairs_apply_clock(pr, 2, dim, carve(workspace, n, dim).totals, n, step_rel,
+                                      clock, step_table, beta1, beta2, eps_adam, weight_decay,
+                                      stream);
+  }
   const bool bf = pairs[0].param_dtype == NCF_DTYPE_BF16;
   return embedding_bwd_reduce(bf, n, dim, num_users, num_items, dy_mf_user, dy_mlp_user,
                               dy_mf_item, dy_mlp_item, pairs[0].p0, pairs[0].p1, pairs[1].p0,

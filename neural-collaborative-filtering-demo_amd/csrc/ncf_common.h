@@ -153,6 +153,54 @@ __device__ __forceinline__ uint32_t ncf_mix32(uint32_t x) {
   return x;
 }
 
+// ---- stochastic rounding of the bf16 tables (NCF_DTYPE_BF16_SR; contract: include/ncf_hip.h).
+// The store of step s on element e = row * D + col of table j of pair `kind` draws
+//   base = mix32(seed ^ 0x9E3779B9 * (2 * (e >> 32) + kind + 1))     (per row)
+//   key  = mix32(base + s)                                           (per row and step)
+//   h    = mix32((uint32)e * 0x9E3779B9 ^ key)                       (per element and step)
+// and rounds with r = h & 0xFFFF (table 0) or h >> 16 (table 1): one mix per element and step
+// serves both tables of the pair.  A pure function of (seed, kind, j, s, e): not of the launch
+// geometry, of the kernel that takes the step, or of when a deferred step is replayed.  A row
+// never straddles a multiple of 2^32 elements (D is a power of two), so base and key are
+// uniform over a row: with one row per wave (replay_uniform) they are scalar work.  The
+// element's word (uint32)e * 0x9E3779B9 (ncf_sr_elem) does not depend on the step: a replay
+// computes it once.  It is there because two rounds of multiply-xorshift on a plain counter
+// leave the top byte of the result measurably non-uniform over 2^22 consecutive elements (a
+// chi-square of 490 where 255 +- 23 is expected; with the multiply, 255: tests/test_sr_stream_cpu).
+__device__ __forceinline__ uint32_t ncf_sr_base(uint32_t seed, int kind, uint32_t e_hi) {
+  return ncf_mix32(seed ^ (0x9E3779B9u * (2u * e_hi + (uint32_t)kind + 1u)));
+}
+__device__ __forceinline__ uint32_t ncf_sr_key(uint32_t base, int32_t step) {
+  return ncf_mix32(base + (uint32_t)step);
+}
+__device__ __forceinline__ uint32_t ncf_sr_elem(uint32_t e_lo) { return e_lo * 0x9E3779B9u; }
+__device__ __forceinline__ uint32_t ncf_sr_bits(uint32_t key, uint32_t elem) {
+  return ncf_mix32(elem ^ key);
+}
+// x rounded to a bf16 value (still held as fp32) with the 16 uniform bits r16:
+// (bits(x) + r16) >> 16 — the magnitude goes up with probability low16(x) / 65536, a value
+// bf16 holds exactly stays, the largest finite magnitudes may reach inf as under nearest-even.
+// NaN takes r16 = 0: x is an arithmetic result, so a quiet NaN, whose high half is what the
+// nearest form stores too (a carry out of an all-ones payload would otherwise flip its sign).
+__device__ __forceinline__ float ncf_sr_round(float x, uint32_t r16) {
+  const uint32_t r = x != x ? 0u : r16;
+  return __uint_as_float((__float_as_uint(x) + r) & 0xFFFF0000u);
+}
+// the table-0 and table-1 values of one element under its 32 bits h
+__device__ __forceinline__ float ncf_sr_round0(float x, uint32_t h) { return ncf_sr_round(x, h & 0xFFFFu); }
+__device__ __forceinline__ float ncf_sr_round1(float x, uint32_t h) { return ncf_sr_round(x, h >> 16); }
+// float4 at element e (the four share e >> 32: e is a multiple of 4), table j of the pair
+template <int J>
+__device__ __forceinline__ float4 ncf_sr_round4(float4 v, uint32_t key, uint32_t e_lo) {
+  float* f = reinterpret_cast<float*>(&v);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t h = ncf_sr_bits(key, ncf_sr_elem(e_lo + i));
+    f[i] = J ? ncf_sr_round1(f[i], h) : ncf_sr_round0(f[i], h);
+  }
+  return v;
+}
+
 // the 64 dropout bits of float4 group idx4: two 32-bit mixes of the group index under keys
 // derived from the 64-bit seed (and the index's high word).  32-bit multiplies only: the
 // 64-bit splitmix of ncf_hash64 costs ~2.5x the VALU work, and the dropout masks are

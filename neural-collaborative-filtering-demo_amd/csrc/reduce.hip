@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_reduce_batch1(const BatchArgs a, float*
 // loads (28 B of scratch per lane) 28 us, with 4 loads (50 registers at D <= 128, no scratch)
 // 27 us; DESIGN §15.
 constexpr int kTailLoads = 4;
-template <int D, bool BF>
+template <int D, bool BF, bool SR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_reduce1_catchup(const BatchArgs a,
                                                          float* __restrict__ scratch, uint32_t nred,
                                                          const PairArgs pa,
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
   }
   if (catchup)
-    pairs_catchup_body<D, BF>(pa, k, b, count, max_n, target_rel, clock, table, s, 0);
+    pairs_catchup_body<D, BF, SR>(pa, k, b, count, max_n, target_rel, clock, table, s, 0);
   else
     reduce1_body<kTailLoads>(a, scratch, b, red);
 }
@@ -214,7 +214,9 @@ template <int D>
 int fused_d(const BatchArgs& a1, float* scratch, uint32_t b1, const Tail& t, hipStream_t st) {
   const uint32_t ncx = (uint32_t)ncf_cdiv(t.max_n * Replay<D>::LPR, 256);
   const dim3 grid(b1 + (uint32_t)t.npairs * ncx);
-  if (t.pa.bf)
+  if (t.pa.sr)
+    hipLaunchKernelGGL((k_reduce1_catchup<D, true, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
+  else if (t.pa.bf)
     hipLaunchKernelGGL((k_reduce1_catchup<D, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
   else
     hipLaunchKernelGGL((k_reduce1_catchup<D, false>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
@@ -315,6 +317,7 @@ extern "C" int ncf_reduce_batch_catchup(const ncf_reduce_list* list, float* scra
                 "ncf_reduce_batch_catchup: bad list");
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table,
                 "ncf_reduce_batch_catchup: bad args");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_reduce_batch_catchup: param_dtype");
   if (max_n <= 0)
     return run_list("ncf_reduce_batch_catchup", list, scratch, scratch_floats, nullptr,
                     (hipStream_t)stream);

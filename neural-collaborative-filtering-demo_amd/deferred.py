@@ -90,7 +90,7 @@ GATHER_FORK_ROWS = 2560
 class DeferredTableAdam:
     def __init__(self, engine, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  sweep_every: int = 64, moments=None, clock=None, overlap_sweep=None,
-                 param_tables=None):
+                 param_tables=None, rounding="nearest", rounding_seed=0):
         self.engine = engine
         self._serial = next(_SERIAL)
         # clock (ncf_step_clock, device): every step-dependent value is read on the device, so
@@ -105,6 +105,20 @@ class DeferredTableAdam:
         self.params = engine.table_params()
         self.tables = dict(param_tables) if param_tables is not None else self.params
         self.bf16 = self.tables["mf_user"].dtype == torch.bfloat16
+        # How the bf16 rows are rounded after every step they take: "nearest" (even), or
+        # "stochastic" under rounding_seed (NCF_DTYPE_BF16_SR, include/ncf_hip.h: the bits are a
+        # function of (seed, kind, table, step, element), so every schedule of the same steps
+        # stores the same values).  Nearest rounding drops in full any update below half a bf16
+        # step of the stored value; stochastic rounding keeps it in expectation.
+        if rounding not in ("nearest", "stochastic"):
+            raise ValueError(f"rounding must be 'nearest' or 'stochastic', got {rounding!r}")
+        self.stochastic = rounding == "stochastic"
+        if self.stochastic and not self.bf16:
+            raise ValueError("stochastic rounding is a store of bf16 tables (param_tables)")
+        if self.stochastic and clock is None:
+            raise ValueError("stochastic rounding needs the device step clock: only the "
+                             "both-kinds entry points carry its seed")
+        self.rounding_seed = int(rounding_seed) & 0xFFFFFFFF
         dev = self.tables["mf_user"].device
         self.state = moments or {k: {"exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
                                  for k, p in self.params.items()}     # (fp32 moments)
@@ -403,7 +417,11 @@ class DeferredTableAdam:
             pr = pairs[k]
             pr.p0, pr.m0, pr.v0, pr.p1, pr.m1, pr.v1 = p0, m0, v0, p1, m1, v1
             pr.stamp, pr.rows = ptr(self.stamp[kind]), self.stamp[kind].numel()
-            pr.param_dtype = _lib.DTYPE_BF16 if self.bf16 else _lib.DTYPE_F32
+            pr.param_dtype = (_lib.DTYPE_BF16_SR if self.stochastic else
+                              _lib.DTYPE_BF16 if self.bf16 else _lib.DTYPE_F32)
+            # (the int32 field takes the seed's 32 bits as a signed value)
+            pr.round_seed = self.rounding_seed - (1 << 32) * (self.rounding_seed >> 31) \
+                if self.stochastic else 0
             if w is not None:
                 pr.row_ids = ptr(w.uniq_u if k == 0 else w.uniq_i)
                 pr.g0, pr.g1 = ptr(w.G[a]), ptr(w.G[b])
@@ -589,6 +607,18 @@ class DeferredTableAdam:
     def _sweep(self, st):
         if self.clock is not None:
             self.flush(st)
+        if self.stochastic:
+            # ncf_adam_sweep_bf16 carries no seed: the rolling sweep with a period of 1 is every
+            # row of both kinds brought to clock->t (= self.t between steps), the same replay
+            self._ensure(self.t + 1)
+            pairs = self.__dict__.get("_sweep_pairs") or self.__dict__.setdefault(
+                "_sweep_pairs", self._pairs())
+            _lib.call("ncf_adam_pairs_sweep_rolling", ctypes.addressof(pairs), 2,
+                      self.engine.model.mlp_embedding_dim, 1, 0, ptr(self.clock),
+                      ptr(self._table), *self._consts(), st)
+            self.synced_t = self.t
+            self.widen()
+            return
         for kind in ("user", "item"):
             self._sweep_range(kind, 0, self.stamp[kind].numel(), st)
         self.synced_t = self.t

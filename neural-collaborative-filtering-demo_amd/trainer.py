@@ -109,13 +109,21 @@ class FusedTrainStep:
     ``clip_grad_norm_`` does between ``backward()`` and ``step()``; the step's norm is
     ``last_grad_norm`` (a 0-dim device tensor).  Such a step runs the table apply as its own launch
     behind the clip (not inside the embedding backward) and leaves the next batch's catch-up to
-    the next step.  ``None`` (default): the step as it is without clipping."""
+    the next step.  ``None`` (default): the step as it is without clipping.
+
+    ``table_rounding="stochastic"`` (bf16 tables on the deferred clock path) rounds the tables
+    after every Adam step stochastically instead of to nearest even, under ``rounding_seed``
+    (``None``: drawn, readable as ``step.rounding_seed``): an update smaller than half a bf16
+    step of the stored value is then kept in expectation instead of dropped every step (DESIGN
+    §21).  The same seed gives the same bits in every schedule of the step, eager or captured,
+    and across an ``export_optimizer_state`` / ``load_optimizer_state`` split."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
                  deferred: bool = True, sweep_every: int = SWEEP_EVERY, graph: bool = False,
                  clock: Optional[bool] = None, warmup: int = 2, concurrent: Optional[bool] = None,
                  overlap_sweep: Optional[bool] = None, table_dtype: torch.dtype = torch.float32,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, table_rounding: str = "nearest",
+                 rounding_seed: Optional[int] = None):
         self.model = model
         self.deferred = None
         # global gradient-norm clipping (clip.py, DESIGN §20): the 2-norm over the four compact
@@ -147,6 +155,16 @@ class FusedTrainStep:
         if table_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("table_dtype must be torch.float32 or torch.bfloat16")
         self.bf16 = table_dtype == torch.bfloat16
+        # (refused before anything of the model is touched)
+        if table_rounding not in ("nearest", "stochastic"):
+            raise ValueError("table_rounding must be 'nearest' or 'stochastic'")
+        if table_rounding == "stochastic":
+            if not self.bf16:
+                raise ValueError("table_rounding='stochastic' rounds bf16 tables "
+                                 "(table_dtype=torch.bfloat16)")
+            if not deferred or clock is False:
+                raise ValueError("table_rounding='stochastic' needs the deferred table Adam on "
+                                 "the step clock (deferred=True, clock not False)")
         self.tables_lp = None
         if self.bf16:
             with torch.no_grad():
@@ -171,6 +189,16 @@ class FusedTrainStep:
             self.clock = torch.tensor([0, self.base_seed], dtype=torch.int64, device=dev)
             eng.clock = self.clock
         self.deferred = None
+        # Rounding of the bf16 tables after every Adam step: "nearest" (even; the default, and
+        # the bits of every release so far) or "stochastic" under rounding_seed (None: drawn as
+        # base_seed is; deferred.py).  The seed sits in the launches' table-pair
+        # struct and the step comes from the device clock: a captured graph needs nothing new.
+        self.table_rounding = table_rounding
+        self.rounding_seed = None
+        if table_rounding == "stochastic":
+            if rounding_seed is None:
+                rounding_seed = int(torch.randint(0, 2 ** 32, (1,)).item())
+            self.rounding_seed = int(rounding_seed) & 0xFFFFFFFF
         if overlap_sweep is None:    # the overlapped rolling sweep (deferred.py): on by default
             overlap_sweep = deferred_mod.OVERLAP_SWEEP
         if deferred:
@@ -178,7 +206,9 @@ class FusedTrainStep:
             self.deferred = DeferredTableAdam(eng, lr, betas, eps, weight_decay, sweep_every,
                                               moments=self.state, clock=self.clock,
                                               overlap_sweep=overlap_sweep and self.clock is not None,
-                                              param_tables=self.tables_lp)
+                                              param_tables=self.tables_lp,
+                                              rounding=table_rounding,
+                                              rounding_seed=self.rounding_seed or 0)
         self.warmup = warmup
         # independent kernels on side streams.  Off by default: measured slower on MI355X, eager
         # (0.63 vs 0.54 ms) and captured (0.71 vs 0.58 ms) — a cross-queue dependency costs more
