@@ -1065,6 +1065,13 @@ int ncf_adam_sweep_rolling(float* p0, float* m0, float* v0, float* p1, float* m1
 #define NCF_DTYPE_F32 0
 #define NCF_DTYPE_BF16 1
 #define NCF_DTYPE_BF16_SR 2
+/* NCF_ADAM_DECOUPLED: a flag ORed into param_dtype (the same in every pair of a call; with
+ * NCF_DTYPE_F32 only): decoupled weight decay, torch.optim.AdamW.  Every pair entry point then
+ * reads step_table in the decoupled layout (NCF_ADAMW_TABLE_STRIDE below) and does not use its
+ * weight_decay argument in the element update: the decay is in the table.
+ * ncf_adam_pairs_apply_gsum_clock returns NCF_ERR_ARG for the flag, and every pair entry point
+ * does for the flag on bf16 rows.                                                             */
+#define NCF_ADAM_DECOUPLED 0x100
 typedef struct ncf_table_pair {
   float *p0, *m0, *v0, *p1, *m1, *v1;
   const float *g0, *g1;
@@ -1188,6 +1195,32 @@ int ncf_adam_flat_clock_close(float* param, const float* grad, float* exp_avg, f
                               int64_t n, const float* step_table, int32_t step_rel,
                               ncf_step_clock* clock, double beta1, double beta2, double eps,
                               double weight_decay, uint64_t base_seed, void* stream);
+
+/* Decoupled weight decay (torch.optim.AdamW, = Adam(decoupled_weight_decay=True)): for step t
+ * with that step's lr,  decay = (float)(1 - lr * wd)  and
+ *   gradient step:       m += (1-b1)(g - m);  v = b2 v + (1-b2) g g
+ *                        p  = fma(ns m, rcp(sqrt(v) ibc + eps), p * decay)
+ *   zero-gradient step:  m  = b1 m;  v = b2 v;  p = fma(m, rcp(sqrt(v) ra + rb), p * decay)
+ * with ns / ibc / ra / rb the four scalars of ncf_adam_step_scalars: no wd term enters g, m or
+ * v, and the decay multiplies p before the Adam term is added (torch's order: mul_, addcdiv_).
+ * An element that never had a gradient keeps m == v == 0 and is multiplied by each owed step's
+ * decay; lr == 0 gives decay == 1 and no step.
+ * Decoupled step table: NCF_ADAMW_TABLE_STRIDE floats per step, step s at [8s .. 8s+7]:
+ * [8s .. 8s+3] the four floats of ncf_adam_step_scalars, [8s+4] that step's decay,
+ * [8s+5 .. 8s+7] zero (the caller lays it out; the decay is one fp32 rounding of a double).  The
+ * decay is read per step: an lr or wd change refills the steps not yet taken, and rows still
+ * behind replay the steps already taken with the values they used.
+ * No entry point is added for it; the existing ones select it:
+ *   - the ncf_table_pair entry points by NCF_ADAM_DECOUPLED in param_dtype (above);
+ *   - ncf_adam_flat_clock / ncf_adam_flat_clock_close by NCF_ADAM_DECOUPLED ORed into step_rel
+ *     (step_rel itself stays below the flag: 2 * NCF_ADAM_DECOUPLED and above is NCF_ERR_ARG): they then read the decoupled table and do not use
+ *     weight_decay;
+ *   - ncf_adam_table / ncf_adam_flat / ncf_adam_table_dense_grad by a NEGATIVE step: step = -t
+ *     is step t under decoupled decay with the lr and weight_decay given (an element without a
+ *     gradient takes the zero-gradient form), bit-identical to the clock forms at step t.
+ * (The reference trainer builds torch.optim.Adam, src/model/trainer.py:71-75; AdamW is the same
+ * call site with the other decay rule.)                                                      */
+#define NCF_ADAMW_TABLE_STRIDE 8
 
 #ifdef __cplusplus
 }

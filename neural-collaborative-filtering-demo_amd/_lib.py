@@ -59,6 +59,8 @@ GRAD_CLIP_MAX_SEGS = DEFINES["NCF_GRAD_CLIP_MAX_SEGS"]
 SHARD_MAX_WORLD = DEFINES["NCF_SHARD_MAX_WORLD"]
 DTYPE_F32, DTYPE_BF16 = DEFINES["NCF_DTYPE_F32"], DEFINES["NCF_DTYPE_BF16"]
 DTYPE_BF16_SR = DEFINES["NCF_DTYPE_BF16_SR"]     # bf16 rows, rounded stochastically
+ADAM_DECOUPLED = DEFINES["NCF_ADAM_DECOUPLED"]   # flag in param_dtype: AdamW's decay rule
+ADAMW_TABLE_STRIDE = DEFINES["NCF_ADAMW_TABLE_STRIDE"]   # floats per step, decoupled table
 
 _MIRRORS = {}   # header struct name -> its ctypes.Structure below
 

@@ -22,11 +22,16 @@ using namespace ncf_adam;
 namespace {
 
 
-template <int D, bool BF = false>
+// DW (here and below): decoupled weight decay, a compile-time choice (step1 / step0 / step4,
+// adam_math.h); dk = the step's decay, not read by the coupled instantiations.  The fixed-step
+// kernels have no step table to take it from: scalars_dw puts it in the scalars' wd slot, which
+// the decoupled element update does not use (the kernel arguments keep their layout).
+template <int D, bool BF = false, bool DW = false>
 __global__ __launch_bounds__(256) void k_adam_table(float* __restrict__ p, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t rows,
                                                     const int32_t* __restrict__ slot,
                                                     const float* __restrict__ G, AdamScalars s) {
+  const float dk = DW ? s.wd : 1.f;   // (scalars_dw: the step's decay rides in the wd slot)
   const int64_t n4 = rows * (D / 4);
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4;
        e += (int64_t)gridDim.x * blockDim.x) {
@@ -35,12 +40,12 @@ __global__ __launch_bounds__(256) void k_adam_table(float* __restrict__ p, float
     const int32_t sl = slot ? slot[row] : -1;
     float4 pp = ldp4<BF>(p, e * 4), mm = ld4(m + e * 4), vv = ld4(v + e * 4);
     if (sl >= 0) {
-      adam4(pp, mm, vv, ld4(G + (int64_t)sl * D + col), s);
+      step4<DW>(pp, mm, vv, ld4(G + (int64_t)sl * D + col), s.neg_step, s.inv_bc2_sqrt, dk, s);
     } else {   // no gradient row this step: the zero-gradient form (as the deferred replay)
-      adam0(pp.x, mm.x, vv.x, s.ra, s.rb, s);
-      adam0(pp.y, mm.y, vv.y, s.ra, s.rb, s);
-      adam0(pp.z, mm.z, vv.z, s.ra, s.rb, s);
-      adam0(pp.w, mm.w, vv.w, s.ra, s.rb, s);
+      step0<DW>(pp.x, mm.x, vv.x, s.ra, s.rb, dk, s);
+      step0<DW>(pp.y, mm.y, vv.y, s.ra, s.rb, dk, s);
+      step0<DW>(pp.z, mm.z, vv.z, s.ra, s.rb, dk, s);
+      step0<DW>(pp.w, mm.w, vv.w, s.ra, s.rb, dk, s);
     }
     stp4<BF>(p, e * 4, pp);
     st4(m + e * 4, mm);
@@ -48,13 +53,15 @@ __global__ __launch_bounds__(256) void k_adam_table(float* __restrict__ p, float
   }
 }
 
+template <bool DW = false>
 __global__ __launch_bounds__(256) void k_adam_flat(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    int64_t n, AdamScalars s) {
+  const float dk = DW ? s.wd : 1.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     float pp = p[i], mm = m[i], vv = v[i];
-    adam1(pp, mm, vv, g[i], s);
+    step1<DW>(pp, mm, vv, g[i], s.neg_step, s.inv_bc2_sqrt, dk, s);
     p[i] = pp;
     m[i] = mm;
     v[i] = vv;
@@ -65,17 +72,19 @@ __global__ __launch_bounds__(256) void k_adam_flat(float* __restrict__ p, const 
 // cases of the optimizer hook): an element whose gradient is exactly zero takes the
 // zero-gradient form, as the row-sparse schedules step the rows that got no gradient (a touched
 // row's gradient is never exactly zero in practice: it comes through the LayerNorm backward).
+template <bool DW = false>
 __global__ __launch_bounds__(256) void k_adam_table_dense_grad(float* __restrict__ p,
                                                                const float* __restrict__ g,
                                                                float* __restrict__ m,
                                                                float* __restrict__ v, int64_t n,
                                                                AdamScalars s) {
+  const float dk = DW ? s.wd : 1.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     float pp = p[i], mm = m[i], vv = v[i];
     const float gg = g[i];
-    if (gg == 0.0f) adam0(pp, mm, vv, s.ra, s.rb, s);
-    else adam1(pp, mm, vv, gg, s);
+    if (gg == 0.0f) step0<DW>(pp, mm, vv, s.ra, s.rb, dk, s);
+    else step1<DW>(pp, mm, vv, gg, s.neg_step, s.inv_bc2_sqrt, dk, s);
     p[i] = pp;
     m[i] = mm;
     v[i] = vv;
@@ -187,6 +196,7 @@ __global__ __launch_bounds__(256) void k_adam_sweep_rolling(TablePtrs t, int64_t
 }
 
 // flat Adam of step clock->t + step_rel with the step table's scalars
+template <bool DW = false>
 __global__ __launch_bounds__(256) void k_adam_flat_clock(float* __restrict__ p,
                                                          const float* __restrict__ g,
                                                          float* __restrict__ m,
@@ -195,12 +205,14 @@ __global__ __launch_bounds__(256) void k_adam_flat_clock(float* __restrict__ p,
                                                          int32_t step_rel,
                                                          const ncf_step_clock* __restrict__ clock,
                                                          AdamScalars s) {
+  constexpr int TS = StepTable<DW>::S;
   const int32_t step = clock->t + step_rel;
-  const float ns = table[4 * step], bc = table[4 * step + 1];
+  const float ns = table[TS * step], bc = table[TS * step + 1];
+  const float dk = DW ? table[TS * step + 4] : 1.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     float pp = p[i], mm = m[i], vv = v[i];
-    adam1(pp, mm, vv, g[i], ns, bc, s);
+    step1<DW>(pp, mm, vv, g[i], ns, bc, dk, s);
     p[i] = pp;
     m[i] = mm;
     v[i] = vv;
@@ -209,13 +221,13 @@ __global__ __launch_bounds__(256) void k_adam_flat_clock(float* __restrict__ p,
 
 // ---- both id kinds per launch (blockIdx.y = kind; PairArgs and the catch-up's body:
 // adam_catchup_dev.h)
-template <int D, bool BF = false, bool SR = false>
+template <int D, bool BF = false, bool SR = false, bool DW = false>
 __global__ __launch_bounds__(256) void k_pairs_catchup(const PairArgs a, const uint32_t* __restrict__ count,
                                                        int64_t max_n, int32_t target_rel,
                                                        const ncf_step_clock* __restrict__ clock,
                                                        const float* __restrict__ table,
                                                        AdamScalars s, int lock) {
-  pairs_catchup_body<D, BF, SR>(a, blockIdx.y, blockIdx.x, count, max_n, target_rel, clock, table, s,
+  pairs_catchup_body<D, BF, SR, DW>(a, blockIdx.y, blockIdx.x, count, max_n, target_rel, clock, table, s,
                             lock);
 }
 
@@ -226,7 +238,7 @@ __global__ __launch_bounds__(256) void k_pairs_catchup(const PairArgs a, const u
 // backward needs can run on another stream beside the forward.  Locked rows (stamp = t |
 // NCF_STAMP_LOCK) compare above any target and are left alone.  Out-of-range ids are skipped
 // (the gather flags them).
-template <int D, bool BF = false, bool SR = false>
+template <int D, bool BF = false, bool SR = false, bool DW = false>
 __global__ __launch_bounds__(256) void k_pairs_catchup_claim(const PairArgs a,
                                                              const int64_t* __restrict__ ids0,
                                                              const int64_t* __restrict__ ids1,
@@ -246,10 +258,10 @@ __global__ __launch_bounds__(256) void k_pairs_catchup_claim(const PairArgs a,
   int32_t from = target;
   if (sub == 0) from = atomicMax(&a.stamp[k][row], target);
   from = __shfl(from, (int)(threadIdx.x & 63) - sub, 64);   // the claim of this row's lane group
-  catch_up_row<D, BF, SR>(a.t[k], row, sub, from, target, table, s, a.seed, k);
+  catch_up_row<D, BF, SR, DW>(a.t[k], row, sub, from, target, table, s, a.seed, k);
 }
 
-template <int D, bool BF = false, bool SR = false>
+template <int D, bool BF = false, bool SR = false, bool DW = false>
 __global__ __launch_bounds__(256) void k_pairs_apply(const PairArgs a, const uint32_t* __restrict__ count,
                                                      int64_t max_n, int32_t step_rel,
                                                      const ncf_step_clock* __restrict__ clock,
@@ -264,7 +276,9 @@ __global__ __launch_bounds__(256) void k_pairs_apply(const PairArgs a, const uin
   const TablePtrs& t = a.t[k];
   const int64_t row = a.ids[k][c];
   const int64_t o = row * D + sub * 4;
-  const float ns = table[4 * step], bc = table[4 * step + 1];
+  constexpr int TS = StepTable<DW>::S;
+  const float ns = table[TS * step], bc = table[TS * step + 1];
+  const float dk = DW ? table[TS * step + 4] : 1.f;
   // every load of both tables before any store: the compiler cannot know the two tables' rows
   // do not alias, and in program order the second table's loads would wait for the first
   // one's stores (two dependent HBM round trips per row instead of one)
@@ -275,8 +289,8 @@ __global__ __launch_bounds__(256) void k_pairs_apply(const PairArgs a, const uin
   if (two) {
     p1 = ldp4<BF>(t.p1, o); m1 = ld4(t.m1 + o); v1 = ld4(t.v1 + o); g1 = ld4(t.G1 + og);
   }
-  adam4(p0, m0, v0, g0, ns, bc, s);
-  if (two) adam4(p1, m1, v1, g1, ns, bc, s);
+  step4<DW>(p0, m0, v0, g0, ns, bc, dk, s);
+  if (two) step4<DW>(p1, m1, v1, g1, ns, bc, dk, s);
   if (SR) {   // this step's bits of the row's elements (ncf_sr_*): exact in bf16 afterwards
     const uint32_t key = ncf_sr_key(ncf_sr_base(a.seed, k, (uint32_t)((uint64_t)o >> 32)), step);
     p0 = ncf_sr_round4<0>(p0, key, (uint32_t)o);
@@ -331,7 +345,7 @@ __global__ __launch_bounds__(256) void k_pairs_apply_gsum(const PairArgs a, cons
 }
 
 // part `part` of `nparts` (consecutive row ranges) of the slice of step clock->t + step_rel
-template <int D, bool BF = false, bool SR = false>
+template <int D, bool BF = false, bool SR = false, bool DW = false>
 __global__ __launch_bounds__(256) void k_pairs_sweep(const PairArgs a, int32_t every,
                                                      int32_t step_rel,
                                                      const ncf_step_clock* __restrict__ clock,
@@ -353,7 +367,7 @@ __global__ __launch_bounds__(256) void k_pairs_sweep(const PairArgs a, int32_t e
     const int64_t row = row0 + e / L;
     const int sub = (int)(e % L);
     const int32_t from = stamp[row];
-    catch_up_row<D, BF, SR>(a.t[k], row, sub, from, target, table, s, a.seed, k);
+    catch_up_row<D, BF, SR, DW>(a.t[k], row, sub, from, target, table, s, a.seed, k);
     if (sub == 0 && from < target) stamp[row] = target;
   }
 }
@@ -374,6 +388,7 @@ __global__ void k_clock_advance(ncf_step_clock* clock, uint64_t base_seed) {
 // k_adam_flat_clock + k_clock_advance in one launch: every block counts itself done in
 // clock->reserved after its threads have read the clock; the last one advances the clock and
 // re-arms the counter (0 between launches).
+template <bool DW = false>
 __global__ __launch_bounds__(256) void k_adam_flat_close(float* __restrict__ p,
                                                          const float* __restrict__ g,
                                                          float* __restrict__ m,
@@ -381,15 +396,17 @@ __global__ __launch_bounds__(256) void k_adam_flat_close(float* __restrict__ p,
                                                          const float* __restrict__ table,
                                                          int32_t step_rel, ncf_step_clock* clock,
                                                          uint64_t base_seed, AdamScalars s) {
+  constexpr int TS = StepTable<DW>::S;
   const int32_t step = clock->t + step_rel;
-  const float ns = table[4 * step], bc = table[4 * step + 1];
+  const float ns = table[TS * step], bc = table[TS * step + 1];
+  const float dk = DW ? table[TS * step + 4] : 1.f;
   // float4 per lane (the flat buffers are 16-B aligned), a short scalar tail; the same adam1 per
   // element as the scalar loop (bit-identical)
   const int64_t n4 = n >> 2;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4;
        e += (int64_t)gridDim.x * blockDim.x) {
     float4 pp = ld4(p + 4 * e), mm = ld4(m + 4 * e), vv = ld4(v + 4 * e);
-    adam4(pp, mm, vv, ld4(g + 4 * e), ns, bc, s);
+    step4<DW>(pp, mm, vv, ld4(g + 4 * e), ns, bc, dk, s);
     st4(p + 4 * e, pp);
     st4(m + 4 * e, mm);
     st4(v + 4 * e, vv);
@@ -397,7 +414,7 @@ __global__ __launch_bounds__(256) void k_adam_flat_close(float* __restrict__ p,
   if (blockIdx.x == 0 && (int64_t)threadIdx.x < n - 4 * n4) {
     const int64_t i = 4 * n4 + threadIdx.x;
     float pp = p[i], mm = m[i], vv = v[i];
-    adam1(pp, mm, vv, g[i], ns, bc, s);
+    step1<DW>(pp, mm, vv, g[i], ns, bc, dk, s);
     p[i] = pp;
     m[i] = mm;
     v[i] = vv;
@@ -425,12 +442,59 @@ int grid_for(int64_t work) {
 
 template <int D>
 int table_d(float* p, float* m, float* v, int64_t rows, const int32_t* slot, const float* G,
-            const AdamScalars& s, hipStream_t st, bool bf = false) {
-  if (bf)
+            const AdamScalars& s, hipStream_t st, bool bf = false, bool dw = false) {
+  if (dw)
+    hipLaunchKernelGGL((k_adam_table<D, false, true>), dim3(grid_for(rows * (D / 4))), dim3(256), 0, st, p, m, v, rows, slot, G, s);
+  else if (bf)
     hipLaunchKernelGGL((k_adam_table<D, true>), dim3(grid_for(rows * (D / 4))), dim3(256), 0, st, p, m, v, rows, slot, G, s);
   else
     hipLaunchKernelGGL((k_adam_table<D, false>), dim3(grid_for(rows * (D / 4))), dim3(256), 0, st, p, m, v, rows, slot, G, s);
   NCF_CHECK_LAUNCH("ncf_adam_table");
+  return NCF_OK;
+}
+
+// the scalars of a decoupled step at a host-given step: no wd term in the element update (k1 =
+// k2 = 0), and the step's decay (float)(1 - lr wd) in the wd slot (k_adam_table's note)
+AdamScalars scalars_dw(double lr, double beta1, double beta2, double eps, double weight_decay,
+                       double step) {
+  AdamScalars s = make_scalars(lr, beta1, beta2, eps, 0.0, step);
+  s.wd = decay_of(lr, weight_decay);
+  return s;
+}
+
+int flat_step(const char* who, bool dw, float* param, const float* grad, float* exp_avg,
+              float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2, double eps,
+              double weight_decay, double step, void* stream) {
+  NCF_CHECK_ARG(n >= 0 && step >= 1, "%s: bad args", who);
+  if (n == 0) return NCF_OK;
+  NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq, "%s: null pointer", who);
+  if (dw)
+    hipLaunchKernelGGL(k_adam_flat<true>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
+                       param, grad, exp_avg, exp_avg_sq, n,
+                       scalars_dw(lr, beta1, beta2, eps, weight_decay, step));
+  else
+    hipLaunchKernelGGL(k_adam_flat<false>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
+                       param, grad, exp_avg, exp_avg_sq, n,
+                       make_scalars(lr, beta1, beta2, eps, weight_decay, step));
+  NCF_CHECK_LAUNCH(who);
+  return NCF_OK;
+}
+
+int dense_grad_step(const char* who, bool dw, float* param, const float* grad, float* exp_avg,
+                    float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
+                    double eps, double weight_decay, double step, void* stream) {
+  NCF_CHECK_ARG(n >= 0 && step >= 1, "%s: bad args", who);
+  if (n == 0) return NCF_OK;
+  NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq, "%s: null pointer", who);
+  if (dw)
+    hipLaunchKernelGGL(k_adam_table_dense_grad<true>, dim3(grid_for(n)), dim3(256), 0,
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
+                       scalars_dw(lr, beta1, beta2, eps, weight_decay, step));
+  else
+    hipLaunchKernelGGL(k_adam_table_dense_grad<false>, dim3(grid_for(n)), dim3(256), 0,
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
+                       make_scalars(lr, beta1, beta2, eps, weight_decay, step));
+  NCF_CHECK_LAUNCH(who);
   return NCF_OK;
 }
 
@@ -448,44 +512,38 @@ int scatter_d(float* dense, const int64_t* uniq, const uint32_t* nu, int kind, c
 // One Adam step over a whole [rows, dim] table (dense-exact; see header).  `slot`/`grad_compact`
 // may be NULL (no touched rows: weight decay only).  `step` is the 1-based step count AFTER
 // increment, as torch's state['step'].
+// A NEGATIVE step (here and in ncf_adam_flat / ncf_adam_table_dense_grad) is step -step under
+// decoupled weight decay (torch.optim.AdamW; include/ncf_hip.h): the dense per-step schedule and
+// the dense-gradient cases, the same element update as the clock forms (adam_math.h).
 extern "C" int ncf_adam_table(float* param, float* exp_avg, float* exp_avg_sq, int64_t rows,
                               int64_t dim, const int32_t* slot, const float* grad_compact,
                               double lr, double beta1, double beta2, double eps,
                               double weight_decay, double step, void* stream) {
+  const bool dw = step < 0;
+  if (dw) step = -step;
   NCF_CHECK_ARG(rows >= 0 && step >= 1, "ncf_adam_table: bad args");
   if (rows == 0) return NCF_OK;
   NCF_CHECK_ARG(param && exp_avg && exp_avg_sq, "ncf_adam_table: null pointer");
-  const AdamScalars s = make_scalars(lr, beta1, beta2, eps, weight_decay, step);
+  const AdamScalars s = dw ? scalars_dw(lr, beta1, beta2, eps, weight_decay, step)
+                           : make_scalars(lr, beta1, beta2, eps, weight_decay, step);
   NCF_DISPATCH_DIM(dim, table_d, param, exp_avg, exp_avg_sq, rows, slot, grad_compact, s,
-                   (hipStream_t)stream);
+                   (hipStream_t)stream, false, dw);
 }
 
 // Adam over a flat fp32 buffer (the dense parameters, packed contiguously by the host).
 extern "C" int ncf_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                              int64_t n, double lr, double beta1, double beta2, double eps,
                              double weight_decay, double step, void* stream) {
-  NCF_CHECK_ARG(n >= 0 && step >= 1, "ncf_adam_flat: bad args");
-  if (n == 0) return NCF_OK;
-  NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq, "ncf_adam_flat: null pointer");
-  const AdamScalars s = make_scalars(lr, beta1, beta2, eps, weight_decay, step);
-  hipLaunchKernelGGL(k_adam_flat, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param,
-                     grad, exp_avg, exp_avg_sq, n, s);
-  NCF_CHECK_LAUNCH("ncf_adam_flat");
-  return NCF_OK;
+  return flat_step("ncf_adam_flat", step < 0, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
+                   beta2, eps, weight_decay, step < 0 ? -step : step, stream);
 }
 
 extern "C" int ncf_adam_table_dense_grad(float* param, const float* grad, float* exp_avg,
                                          float* exp_avg_sq, int64_t n, double lr, double beta1,
                                          double beta2, double eps, double weight_decay,
                                          double step, void* stream) {
-  NCF_CHECK_ARG(n >= 0 && step >= 1, "ncf_adam_table_dense_grad: bad args");
-  if (n == 0) return NCF_OK;
-  NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq, "ncf_adam_table_dense_grad: null pointer");
-  const AdamScalars s = make_scalars(lr, beta1, beta2, eps, weight_decay, step);
-  hipLaunchKernelGGL(k_adam_table_dense_grad, dim3(grid_for(n)), dim3(256), 0,
-                     (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, s);
-  NCF_CHECK_LAUNCH("ncf_adam_table_dense_grad");
-  return NCF_OK;
+  return dense_grad_step("ncf_adam_table_dense_grad", step < 0, param, grad, exp_avg, exp_avg_sq,
+                         n, lr, beta1, beta2, eps, weight_decay, step < 0 ? -step : step, stream);
 }
 
 extern "C" int ncf_scatter_compact_rows(float* dense_grad, int64_t dim, const int64_t* uniq,
@@ -532,7 +590,9 @@ template <int D>
 int pairs_catchup_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, int32_t rel,
                     const ncf_step_clock* clock, const float* table, AdamScalars s,
                     hipStream_t st, int lock = 0) {
-  if (a.sr)
+  if (a.dw)
+    hipLaunchKernelGGL((k_pairs_catchup<D, false, false, true>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
+  else if (a.sr)
     hipLaunchKernelGGL((k_pairs_catchup<D, true, true>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
   else if (a.bf)
     hipLaunchKernelGGL((k_pairs_catchup<D, true>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
@@ -545,7 +605,9 @@ int pairs_catchup_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, int
 template <int D>
 int pairs_apply_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, int32_t rel,
                   const ncf_step_clock* clock, const float* table, AdamScalars s, hipStream_t st) {
-  if (a.sr)
+  if (a.dw)
+    hipLaunchKernelGGL((k_pairs_apply<D, false, false, true>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
+  else if (a.sr)
     hipLaunchKernelGGL((k_pairs_apply<D, true, true>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
   else if (a.bf)
     hipLaunchKernelGGL((k_pairs_apply<D, true>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
@@ -581,7 +643,9 @@ int pairs_sweep_d(PairArgs a, int n, int32_t every, int32_t rel, const ncf_step_
   for (int k = 0; k < n; ++k) slice = max(slice, (a.rows[k] + every - 1) / every);
   slice = (slice + nparts - 1) / nparts;
   const int gx = (int)min((int64_t)grid_for(slice * Replay<D>::LPR), 256 * g_sweep_blocks_per_cu);
-  if (a.sr)
+  if (a.dw)
+    hipLaunchKernelGGL((k_pairs_sweep<D, false, false, true>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
+  else if (a.sr)
     hipLaunchKernelGGL((k_pairs_sweep<D, true, true>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
   else if (a.bf)
     hipLaunchKernelGGL((k_pairs_sweep<D, true>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
@@ -599,6 +663,55 @@ int sweep_d(TablePtrs t, int64_t row0, int64_t rows, int32_t* stamp, int32_t tar
   else
     hipLaunchKernelGGL((k_adam_sweep<D, false>), dim3(grid_for(rows * Replay<D>::LPR)), dim3(256), 0, st, t, row0, rows, stamp, target, table, s);
   NCF_CHECK_LAUNCH("ncf_adam_sweep");
+  return NCF_OK;
+}
+
+// the flat clock forms of both decay rules (dw: the decoupled table and element update)
+int flat_clock(const char* who, bool dw, float* param, const float* grad, float* exp_avg,
+               float* exp_avg_sq, int64_t n, const float* step_table, int32_t step_rel,
+               const ncf_step_clock* clock, double beta1, double beta2, double eps,
+               double weight_decay, void* stream) {
+  // (step_rel with the flag stripped: a value at or above the flag would be read as flagged)
+  NCF_CHECK_ARG(n >= 0 && step_rel < NCF_ADAM_DECOUPLED, "%s: bad args", who);
+  if (n == 0) return NCF_OK;
+  NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step_table && clock,
+                "%s: null pointer", who);
+  const AdamScalars s = consts_of(beta1, beta2, eps, dw ? 0.0 : weight_decay);
+  if (dw)
+    hipLaunchKernelGGL(k_adam_flat_clock<true>, dim3(grid_for(n)), dim3(256), 0,
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, step_table,
+                       step_rel, clock, s);
+  else
+    hipLaunchKernelGGL(k_adam_flat_clock<false>, dim3(grid_for(n)), dim3(256), 0,
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, step_table,
+                       step_rel, clock, s);
+  NCF_CHECK_LAUNCH(who);
+  return NCF_OK;
+}
+
+int flat_close(const char* who, bool dw, float* param, const float* grad, float* exp_avg,
+               float* exp_avg_sq, int64_t n, const float* step_table, int32_t step_rel,
+               ncf_step_clock* clock, double beta1, double beta2, double eps,
+               double weight_decay, uint64_t base_seed, void* stream) {
+  NCF_CHECK_ARG(n >= 1 && param && grad && exp_avg && exp_avg_sq && step_table && clock &&
+                    step_rel < NCF_ADAM_DECOUPLED,
+                "%s: bad args", who);
+  NCF_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
+                "%s: buffers must be 16-B aligned", who);
+  // every block's arrival is one same-address atomic on the clock word: at most 64 blocks
+  // (was one per 256 elements, 328 at C2: the serialised atomics held the launch ~3 us)
+  int64_t nb = ((n >> 2) + 255) / 256;
+  nb = nb < 1 ? 1 : (nb > 64 ? 64 : nb);
+  const AdamScalars s = consts_of(beta1, beta2, eps, dw ? 0.0 : weight_decay);
+  if (dw)
+    hipLaunchKernelGGL(k_adam_flat_close<true>, dim3((unsigned)nb), dim3(256), 0,
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, step_table,
+                       step_rel, clock, base_seed, s);
+  else
+    hipLaunchKernelGGL(k_adam_flat_close<false>, dim3((unsigned)nb), dim3(256), 0,
+                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, step_table,
+                       step_rel, clock, base_seed, s);
+  NCF_CHECK_LAUNCH(who);
   return NCF_OK;
 }
 }  // namespace
@@ -739,19 +852,15 @@ extern "C" int ncf_adam_sweep_rolling(float* p0, float* m0, float* v0, float* p1
                    step_table, consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream);
 }
 
+// NCF_ADAM_DECOUPLED ORed into step_rel (here and in the closing form): the decoupled step table
+// and element update (weight_decay is then not used: the decay is in the table)
 extern "C" int ncf_adam_flat_clock(float* param, const float* grad, float* exp_avg,
                                    float* exp_avg_sq, int64_t n, const float* step_table,
                                    int32_t step_rel, const ncf_step_clock* clock, double beta1,
                                    double beta2, double eps, double weight_decay, void* stream) {
-  NCF_CHECK_ARG(n >= 0, "ncf_adam_flat_clock: bad args");
-  if (n == 0) return NCF_OK;
-  NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step_table && clock,
-                "ncf_adam_flat_clock: null pointer");
-  hipLaunchKernelGGL(k_adam_flat_clock, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
-                     param, grad, exp_avg, exp_avg_sq, n, step_table, step_rel, clock,
-                     consts_of(beta1, beta2, eps, weight_decay));
-  NCF_CHECK_LAUNCH("ncf_adam_flat_clock");
-  return NCF_OK;
+  return flat_clock("ncf_adam_flat_clock", step_rel >= 0 && (step_rel & NCF_ADAM_DECOUPLED), param, grad,
+                    exp_avg, exp_avg_sq, n, step_table, step_rel >= 0 ? step_rel & ~NCF_ADAM_DECOUPLED : step_rel, clock,
+                    beta1, beta2, eps, weight_decay, stream);
 }
 
 extern "C" int ncf_adam_flat_clock_close(float* param, const float* grad, float* exp_avg,
@@ -759,19 +868,9 @@ extern "C" int ncf_adam_flat_clock_close(float* param, const float* grad, float*
                                          int32_t step_rel, ncf_step_clock* clock, double beta1,
                                          double beta2, double eps, double weight_decay,
                                          uint64_t base_seed, void* stream) {
-  NCF_CHECK_ARG(n >= 1 && param && grad && exp_avg && exp_avg_sq && step_table && clock,
-                "ncf_adam_flat_clock_close: bad args");
-  NCF_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
-                "ncf_adam_flat_clock_close: buffers must be 16-B aligned");
-  // every block's arrival is one same-address atomic on the clock word: at most 64 blocks
-  // (was one per 256 elements, 328 at C2: the serialised atomics held the launch ~3 us)
-  int64_t nb = ((n >> 2) + 255) / 256;
-  nb = nb < 1 ? 1 : (nb > 64 ? 64 : nb);
-  hipLaunchKernelGGL(k_adam_flat_close, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
-                     param, grad, exp_avg, exp_avg_sq, n, step_table, step_rel, clock, base_seed,
-                     consts_of(beta1, beta2, eps, weight_decay));
-  NCF_CHECK_LAUNCH("ncf_adam_flat_clock_close");
-  return NCF_OK;
+  return flat_close("ncf_adam_flat_clock_close", step_rel >= 0 && (step_rel & NCF_ADAM_DECOUPLED), param,
+                    grad, exp_avg, exp_avg_sq, n, step_table, step_rel >= 0 ? step_rel & ~NCF_ADAM_DECOUPLED : step_rel,
+                    clock, beta1, beta2, eps, weight_decay, base_seed, stream);
 }
 
 extern "C" int ncf_adam_pairs_catchup_clock(const ncf_table_pair* pairs, int npairs, int64_t dim,
@@ -815,7 +914,10 @@ int pairs_claim_d(PairArgs a, int npairs, const int64_t* ids0, const int64_t* id
                   int32_t rel, const ncf_step_clock* clock, const float* table, AdamScalars s,
                   hipStream_t st) {
   const dim3 grid((unsigned)ncf_cdiv(n * Replay<D>::LPR, 256), npairs);
-  if (a.sr)
+  if (a.dw)
+    hipLaunchKernelGGL((k_pairs_catchup_claim<D, false, false, true>), grid, dim3(256), 0, st, a, ids0,
+                       ids1, n, rel, clock, table, s);
+  else if (a.sr)
     hipLaunchKernelGGL((k_pairs_catchup_claim<D, true, true>), grid, dim3(256), 0, st, a, ids0, ids1, n,
                        rel, clock, table, s);
   else if (a.bf)
@@ -875,8 +977,10 @@ extern "C" int ncf_adam_pairs_apply_gsum_clock(const ncf_table_pair* pairs, int 
   NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table && got &&
                     pos0 && pos1 && world >= 1,
                 "ncf_adam_pairs_apply_gsum_clock: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs) && pairs[0].param_dtype != NCF_DTYPE_BF16_SR,
-                "ncf_adam_pairs_apply_gsum_clock: param_dtype (no stochastic rounding here)");
+  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs) && pairs[0].param_dtype != NCF_DTYPE_BF16_SR &&
+                    !(pairs[0].param_dtype & NCF_ADAM_DECOUPLED),
+                "ncf_adam_pairs_apply_gsum_clock: param_dtype (no stochastic rounding and no "
+                "decoupled weight decay here)");
   for (int k = 0; k < npairs; ++k)
     NCF_CHECK_ARG(pairs[k].p1, "ncf_adam_pairs_apply_gsum_clock: both tables of a pair");
   if (max_n <= 0) return NCF_OK;

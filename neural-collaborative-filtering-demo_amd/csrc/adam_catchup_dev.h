@@ -43,39 +43,47 @@ struct Replay {
 // SR (with BF): the parameter is rounded stochastically after every step, each step with its
 // own bits (ncf_sr_*, ncf_common.h): sr_base is the row's ncf_sr_base, wave-uniform like the
 // bounds, so a step's key is scalar work; e_lo the low word of the lane's first element.
-template <int EPL, bool PAIR, bool BF = false, bool SR = false>
+// DW: decoupled weight decay (adam_math.h): the table has StepTable<DW>::S floats per step and
+// the step's decay travels with ra / rb, a third scalar per owed step through the same scalar
+// loads and the same prefetch (NS scalars per step; the coupled form keeps its two).
+template <int EPL, bool PAIR, bool BF = false, bool SR = false, bool DW = false>
 __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, float* p1,
                                                float* m1, float* v1, int32_t from, int32_t to,
                                                const float* __restrict__ table,
                                                const AdamScalars& s, uint32_t sr_base = 0,
                                                uint32_t e_lo = 0) {
   constexpr int C = 8;                 // steps per chunk
+  constexpr int TS = StepTable<DW>::S; // floats per step of the table
+  constexpr int NS = DW ? 3 : 2;       // scalars a zero-gradient step reads: ra, rb (, decay)
   int32_t q = from + 1;
   uint32_t ew[EPL];                    // SR: the elements' words, the same at every step
 #pragma unroll
   for (int j = 0; j < EPL; ++j) ew[j] = SR ? ncf_sr_elem(e_lo + j * 64) : 0u;
-  float sc[2 * C];
+  float sc[NS * C];
 #pragma unroll
   for (int k = 0; k < C; ++k) {
-    sc[2 * k] = table[4 * (q + k) + 2];
-    sc[2 * k + 1] = table[4 * (q + k) + 3];
+    sc[NS * k] = table[TS * (q + k) + 2];
+    sc[NS * k + 1] = table[TS * (q + k) + 3];
+    if (DW) sc[NS * k + NS - 1] = table[TS * (q + k) + 4];
   }
   while (q + C - 1 <= to) {
-    float nx[2 * C];
+    float nx[NS * C];
 #pragma unroll
     for (int k = 0; k < C; ++k) {
-      nx[2 * k] = table[4 * (q + C + k) + 2];
-      nx[2 * k + 1] = table[4 * (q + C + k) + 3];
+      nx[NS * k] = table[TS * (q + C + k) + 2];
+      nx[NS * k + 1] = table[TS * (q + C + k) + 3];
+      if (DW) nx[NS * k + NS - 1] = table[TS * (q + C + k) + 4];
     }
     __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ahead of this chunk's steps
 #pragma unroll
     for (int k = 0; k < C; ++k) {
       const uint32_t key = SR ? ncf_sr_key(sr_base, q + k) : 0u;
+      const float dk = DW ? sc[NS * k + NS - 1] : 1.f;
 #pragma unroll
       for (int j = 0; j < EPL; ++j) {
-        adam0(p0[j], m0[j], v0[j], sc[2 * k], sc[2 * k + 1], s);
+        step0<DW>(p0[j], m0[j], v0[j], sc[NS * k], sc[NS * k + 1], dk, s);
         if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);   // bf16 tables: stored (rounded) every step
-        if (PAIR) adam0(p1[j], m1[j], v1[j], sc[2 * k], sc[2 * k + 1], s);
+        if (PAIR) step0<DW>(p1[j], m1[j], v1[j], sc[NS * k], sc[NS * k + 1], dk, s);
         if (PAIR && BF && !SR) p1[j] = ncf_round_bf16(p1[j]);
         if (SR) {
           const uint32_t h = ncf_sr_bits(key, ew[j]);
@@ -85,18 +93,19 @@ __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, 
       }
     }
 #pragma unroll
-    for (int k = 0; k < 2 * C; ++k) sc[k] = nx[k];
+    for (int k = 0; k < NS * C; ++k) sc[k] = nx[k];
     q += C;
   }
 #pragma unroll
   for (int k = 0; k < C - 1; ++k) {    // the last to - q + 1 < C steps
     if (q + k > to) break;
     const uint32_t key = SR ? ncf_sr_key(sr_base, q + k) : 0u;
+    const float dk = DW ? sc[NS * k + NS - 1] : 1.f;
 #pragma unroll
     for (int j = 0; j < EPL; ++j) {
-      adam0(p0[j], m0[j], v0[j], sc[2 * k], sc[2 * k + 1], s);
+      step0<DW>(p0[j], m0[j], v0[j], sc[NS * k], sc[NS * k + 1], dk, s);
       if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);
-      if (PAIR) adam0(p1[j], m1[j], v1[j], sc[2 * k], sc[2 * k + 1], s);
+      if (PAIR) step0<DW>(p1[j], m1[j], v1[j], sc[NS * k], sc[NS * k + 1], dk, s);
       if (PAIR && BF && !SR) p1[j] = ncf_round_bf16(p1[j]);
       if (SR) {
         const uint32_t h = ncf_sr_bits(key, ew[j]);
@@ -108,12 +117,14 @@ __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, 
 }
 
 // SR: stochastic rounding under `seed` for the tables of pair `kind` (ncf_sr_*)
-template <int D, bool BF = false, bool SR = false>
+template <int D, bool BF = false, bool SR = false, bool DW = false>
 __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, int sub, int32_t from,
                                              int32_t to, const float* __restrict__ table,
                                              const AdamScalars& s, uint32_t seed = 0,
                                              int kind = 0) {
   static_assert(BF || !SR, "stochastic rounding is a store of bf16 rows");
+  static_assert(!DW || !BF, "decoupled weight decay steps fp32 rows");
+  constexpr int TS = StepTable<DW>::S;
   constexpr int EPL = Replay<D>::EPL, LPR = Replay<D>::LPR;
   if (Replay<D>::LPR == 64) {   // the whole wave holds this row: make the bounds scalar
     from = __builtin_amdgcn_readfirstlane(from);
@@ -138,16 +149,17 @@ __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, in
       p1[j] = ldp<BF>(t.p1, o + j * LPR); m1[j] = t.m1[o + j * LPR]; v1[j] = t.v1[o + j * LPR];
     }
     if (Replay<D>::LPR == 64) {
-      replay_uniform<EPL, true, BF, SR>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
+      replay_uniform<EPL, true, BF, SR, DW>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
     } else {
 #pragma unroll 2
       for (int32_t q = from + 1; q <= to; ++q) {
-        const float ra = table[4 * q + 2], rb = table[4 * q + 3];
+        const float ra = table[TS * q + 2], rb = table[TS * q + 3];
+      const float dk = DW ? table[TS * q + 4] : 1.f;
         const uint32_t key = SR ? ncf_sr_key(base, q) : 0u;
 #pragma unroll
         for (int j = 0; j < EPL; ++j) {
-          adam0(p0[j], m0[j], v0[j], ra, rb, s);
-          adam0(p1[j], m1[j], v1[j], ra, rb, s);
+          step0<DW>(p0[j], m0[j], v0[j], ra, rb, dk, s);
+          step0<DW>(p1[j], m1[j], v1[j], ra, rb, dk, s);
           if (BF && !SR) { p0[j] = ncf_round_bf16(p0[j]); p1[j] = ncf_round_bf16(p1[j]); }
           if (SR) {
             const uint32_t h = ncf_sr_bits(key, ncf_sr_elem(e_lo + j * LPR));
@@ -162,15 +174,16 @@ __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, in
       stp<BF>(t.p1, o + j * LPR, p1[j]); t.m1[o + j * LPR] = m1[j]; t.v1[o + j * LPR] = v1[j];
     }
   } else if (Replay<D>::LPR == 64) {
-    replay_uniform<EPL, false, BF, SR>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
+    replay_uniform<EPL, false, BF, SR, DW>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
   } else {
 #pragma unroll 2
     for (int32_t q = from + 1; q <= to; ++q) {
-      const float ra = table[4 * q + 2], rb = table[4 * q + 3];
+      const float ra = table[TS * q + 2], rb = table[TS * q + 3];
+      const float dk = DW ? table[TS * q + 4] : 1.f;
       const uint32_t key = SR ? ncf_sr_key(base, q) : 0u;
 #pragma unroll
       for (int j = 0; j < EPL; ++j) {
-        adam0(p0[j], m0[j], v0[j], ra, rb, s);
+        step0<DW>(p0[j], m0[j], v0[j], ra, rb, dk, s);
         if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);
         if (SR) p0[j] = ncf_sr_round0(p0[j], ncf_sr_bits(key, ncf_sr_elem(e_lo + j * LPR)));
       }
@@ -191,12 +204,17 @@ struct PairArgs {
   int bf;            // parameter rows are bf16 (host-side dispatch only)
   int sr;            // ... and rounded stochastically (NCF_DTYPE_BF16_SR; host-side dispatch)
   uint32_t seed;     // round_seed of the stochastic rounding (ncf_sr_base)
+  int dw;            // decoupled weight decay (NCF_ADAM_DECOUPLED; host-side dispatch)
 };
+static_assert(sizeof(PairArgs) == 192, "PairArgs: dw sits in the tail padding (kernel arguments)");
 
 // whether the n pairs name one parameter dtype this build knows (NCF_DTYPE_*)
 inline bool pair_dtypes_ok(const ncf_table_pair* p, int n) {
   for (int k = 0; k < n && k < 2; ++k)
     if (p[k].param_dtype != p[0].param_dtype || p[k].round_seed != p[0].round_seed) return false;
+  // (decoupled weight decay: fp32 rows only)
+  if (p[0].param_dtype & NCF_ADAM_DECOUPLED)
+    return p[0].param_dtype == (NCF_DTYPE_F32 | NCF_ADAM_DECOUPLED);
   return p[0].param_dtype == NCF_DTYPE_F32 || p[0].param_dtype == NCF_DTYPE_BF16 ||
          p[0].param_dtype == NCF_DTYPE_BF16_SR;
 }
@@ -210,15 +228,17 @@ inline PairArgs pair_args(const ncf_table_pair* p, int n) {
     a.stamp[k] = p[k].stamp;
     a.rows[k] = p[k].rows;
   }
-  a.sr = p[0].param_dtype == NCF_DTYPE_BF16_SR;
-  a.bf = a.sr || p[0].param_dtype == NCF_DTYPE_BF16;
+  a.dw = (p[0].param_dtype & NCF_ADAM_DECOUPLED) != 0;
+  const int32_t dt = p[0].param_dtype & ~NCF_ADAM_DECOUPLED;
+  a.sr = dt == NCF_DTYPE_BF16_SR;
+  a.bf = a.sr || dt == NCF_DTYPE_BF16;
   a.seed = (uint32_t)p[0].round_seed;
   return a;
 }
 
 // Block bx (of ncf_cdiv(max_n * Replay<D>::LPR, 256), 256 threads) of the catch-up of kind k's
 // listed rows ids[k][0 .. count[k]) to clock->t + target_rel.
-template <int D, bool BF, bool SR = false>
+template <int D, bool BF, bool SR = false, bool DW = false>
 __device__ __forceinline__ void pairs_catchup_body(const PairArgs& a, int k, uint32_t bx,
                                                    const uint32_t* __restrict__ count,
                                                    int64_t max_n, int32_t target_rel,
@@ -234,7 +254,7 @@ __device__ __forceinline__ void pairs_catchup_body(const PairArgs& a, int k, uin
   const int64_t row = a.ids[k][c];
   int32_t* stamp = a.stamp[k];
   const int32_t from = stamp[row];
-  catch_up_row<D, BF, SR>(a.t[k], row, sub, from, target, table, s, a.seed, k);
+  catch_up_row<D, BF, SR, DW>(a.t[k], row, sub, from, target, table, s, a.seed, k);
   // lock: every listed row is marked in flight (current through target, its gradient step still
   // to come: the step's apply writes the plain stamp back); replays of other rows skip it.  A
   // listed row that is locked already, or ahead of the target, keeps its stamp: it was not

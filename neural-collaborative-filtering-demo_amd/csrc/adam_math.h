@@ -9,7 +9,7 @@ namespace ncf_adam {
 namespace {
 
 struct AdamScalars {
-  float neg_step, w1, b2, c2, inv_bc2_sqrt, eps, wd;
+  float neg_step, w1, b2, c2, inv_bc2_sqrt, eps, wd;   // (wd: see scalars_dw, adam.hip)
   float b1, k1, k2;   // zero-gradient step: beta1, (1-beta1) wd, (1-beta2) wd^2
   float ra, rb;       // zero-gradient step s: inv_bc2_sqrt / neg_step, eps / neg_step
 };
@@ -61,6 +61,65 @@ __device__ __forceinline__ void adam4(float4& p, float4& m, float4& v, float4 g,
 __device__ __forceinline__ void adam4(float4& p, float4& m, float4& v, float4 g, const AdamScalars& s) {
   adam4(p, m, v, g, s.neg_step, s.inv_bc2_sqrt, s);
 }
+
+// ---- decoupled weight decay (torch.optim.AdamW; NCF_ADAM_DECOUPLED) -----------------------
+// The decay multiplies the parameter before the Adam term is added (torch: param.mul_(1 - lr wd),
+// then addcdiv_) and no wd term enters g, m or v:
+//   m += (1-b1)(g - m);  v = b2 v + (1-b2) g^2;  p = fma(ns m, rcp(sqrt(v) ibc + eps), p dk)
+// dk = (float)(1 - lr wd) of that step (decay_of), a per-step scalar beside ns / ibc / ra / rb.
+__device__ __forceinline__ void adamw1(float& p, float& m, float& v, float g, float neg_step,
+                                       float inv_bc, float dk, const AdamScalars& s) {
+  m = __builtin_fmaf(s.w1, g - m, m);
+  v = __builtin_fmaf(s.c2 * g, g, v * s.b2);
+  const float denom = __builtin_fmaf(__builtin_amdgcn_sqrtf(v), inv_bc, s.eps);
+  p = __builtin_fmaf(neg_step * m, __builtin_amdgcn_rcpf(denom), p * dk);
+}
+
+// The zero-gradient step (8 VALU ops, 2 transcendental): m = b1 m; v = b2 v;
+//   p = fma(m, rcp(sqrt(v) ra + rb), p dk)
+// A never-touched element (m == v == 0) keeps m == v == 0 and takes p = p dk exactly (0 * rcp(rb)
+// is a zero: rb is finite and nonzero, -3e38 at lr == 0).
+__device__ __forceinline__ void adamw0(float& p, float& m, float& v, float ra, float rb, float dk,
+                                       const AdamScalars& s) {
+  m = s.b1 * m;
+  v = v * s.b2;
+  const float den = __builtin_fmaf(__builtin_amdgcn_sqrtf(v), ra, rb);
+  p = __builtin_fmaf(m, __builtin_amdgcn_rcpf(den), p * dk);
+}
+
+// The element update of a kernel instantiated for one decay rule (DW: decoupled).  A compile-time
+// choice: the coupled instantiations are adam1 / adam0 as they stand (dk unused, no multiply).
+template <bool DW>
+__device__ __forceinline__ void step1(float& p, float& m, float& v, float g, float ns, float bc,
+                                      float dk, const AdamScalars& s) {
+  if (DW) adamw1(p, m, v, g, ns, bc, dk, s);
+  else adam1(p, m, v, g, ns, bc, s);
+}
+
+template <bool DW>
+__device__ __forceinline__ void step0(float& p, float& m, float& v, float ra, float rb, float dk,
+                                      const AdamScalars& s) {
+  if (DW) adamw0(p, m, v, ra, rb, dk, s);
+  else adam0(p, m, v, ra, rb, s);
+}
+
+template <bool DW>
+__device__ __forceinline__ void step4(float4& p, float4& m, float4& v, float4 g, float ns,
+                                      float bc, float dk, const AdamScalars& s) {
+  step1<DW>(p.x, m.x, v.x, g.x, ns, bc, dk, s);
+  step1<DW>(p.y, m.y, v.y, g.y, ns, bc, dk, s);
+  step1<DW>(p.z, m.z, v.z, g.z, ns, bc, dk, s);
+  step1<DW>(p.w, m.w, v.w, g.w, ns, bc, dk, s);
+}
+
+// floats per step of the per-step scalar table a kernel reads: 4 (ncf_adam_step_scalars) or
+// NCF_ADAMW_TABLE_STRIDE with the step's decay at index 4 (include/ncf_hip.h)
+template <bool DW>
+struct StepTable {
+  static constexpr int S = DW ? NCF_ADAMW_TABLE_STRIDE : 4;
+};
+
+inline float decay_of(double lr, double wd) { return (float)(1.0 - lr * wd); }
 
 inline AdamScalars make_scalars(double lr, double beta1, double beta2, double eps, double wd, double step) {
   AdamScalars s;

@@ -431,7 +431,8 @@ extern "C" int ncf_embedding_bwd_reduce_apply_clock(
     void* stream) {
   NCF_CHECK_ARG(pairs && clock && step_table, "ncf_embedding_bwd_reduce_apply_clock: bad args");
   NCF_CHECK_ARG(pairs[0].param_dtype == NCF_DTYPE_F32 || pairs[0].param_dtype == NCF_DTYPE_BF16 ||
-                    pairs[0].param_dtype == NCF_DTYPE_BF16_SR,
+                    pairs[0].param_dtype == NCF_DTYPE_BF16_SR ||
+                    pairs[0].param_dtype == (NCF_DTYPE_F32 | NCF_ADAM_DECOUPLED),
                 "ncf_embedding_bwd_reduce_apply_clock: param_dtype");
   ApplyArgs ap{};
   for (int k = 0; k < 2; ++k) {
@@ -449,7 +450,8 @@ extern "C" int ncf_embedding_bwd_reduce_apply_clock(
   ap.s = ncf_adam::consts_of(beta1, beta2, eps_adam, weight_decay);
   ap.step_rel = step_rel;
   ap.on = 1;
-  if (pairs[0].param_dtype == NCF_DTYPE_BF16_SR) {
+  const bool decoupled = (pairs[0].param_dtype & NCF_ADAM_DECOUPLED) != 0;
+  if (pairs[0].param_dtype == NCF_DTYPE_BF16_SR || decoupled) {
     // Stochastic rounding: the reduce as ncf_embedding_bwd_reduce_bf16 runs it, then the apply
     // as its own launch (ncf_adam_pairs_apply_clock over this call's unique rows and compact
     // gradients; totals[k] of the workspace is num_unique[k]).  Not inside the reduce: a third
@@ -457,8 +459,10 @@ extern "C" int ncf_embedding_bwd_reduce_apply_clock(
     // two bit for bit (measured: moments one fp32 ulp off on 15 % of the touched elements;
     // supposed cause: its plain multiply-adds contracted differently), and every schedule of
     // a step has to store the same bits.
+    // Decoupled weight decay (NCF_ADAM_DECOUPLED, fp32 rows) takes the same route for the same
+    // reason: its apply is k_pairs_apply's decoupled instantiation, behind the unchanged reduce.
     const int rc = embedding_bwd_reduce(
-        true, n, dim, num_users, num_items, dy_mf_user, dy_mlp_user, dy_mf_item, dy_mlp_item,
+        !decoupled, n, dim, num_users, num_items, dy_mf_user, dy_mlp_user, dy_mf_item, dy_mlp_item,
         pairs[0].p0, pairs[0].p1, pairs[1].p0, pairs[1].p1, mf_gamma, mlp_gamma, eps, grad_mf_user,
         grad_mlp_user, grad_mf_item, grad_mlp_item, uniq_users, uniq_items, grad_mf_gamma,
         grad_mf_beta, grad_mlp_gamma, grad_mlp_beta, workspace, workspace_bytes, defer, stream);

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_reduce_batch1(const BatchArgs a, float*
 // loads (28 B of scratch per lane) 28 us, with 4 loads (50 registers at D <= 128, no scratch)
 // 27 us; DESIGN §15.
 constexpr int kTailLoads = 4;
-template <int D, bool BF, bool SR = false>
+template <int D, bool BF, bool SR = false, bool DW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_reduce1_catchup(const BatchArgs a,
                                                          float* __restrict__ scratch, uint32_t nred,
                                                          const PairArgs pa,
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
   }
   if (catchup)
-    pairs_catchup_body<D, BF, SR>(pa, k, b, count, max_n, target_rel, clock, table, s, 0);
+    pairs_catchup_body<D, BF, SR, DW>(pa, k, b, count, max_n, target_rel, clock, table, s, 0);
   else
     reduce1_body<kTailLoads>(a, scratch, b, red);
 }
@@ -210,11 +210,22 @@ struct Tail {
   AdamScalars s;
 };
 
+// The widest rows whose decoupled catch-up rides in the fused launch.  The decoupled replay keeps
+// more steps in flight per lane (m and v do not depend on p, so the compiler runs their chains
+// ahead); held to the fused kernel's 64 registers at D = 256 it spilled 116 B per lane (compiler
+// resource report), so that width takes the reduce and the catch-up as two launches: same bits.
+constexpr int kDwFusedMaxDim = 128;
+
 template <int D>
 int fused_d(const BatchArgs& a1, float* scratch, uint32_t b1, const Tail& t, hipStream_t st) {
   const uint32_t ncx = (uint32_t)ncf_cdiv(t.max_n * Replay<D>::LPR, 256);
   const dim3 grid(b1 + (uint32_t)t.npairs * ncx);
-  if (t.pa.sr)
+  if (t.pa.dw) {   // decoupled weight decay (NCF_ADAM_DECOUPLED): the decoupled step table
+    // (D = 256 is not fused, kDwFusedMaxDim: ncf_reduce_batch_catchup makes the two launches)
+    if constexpr (D <= kDwFusedMaxDim)
+      hipLaunchKernelGGL((k_reduce1_catchup<D, false, false, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
+    // (wider rows never get here: no instantiation of the fused kernel for them)
+  } else if (t.pa.sr)
     hipLaunchKernelGGL((k_reduce1_catchup<D, true, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
   else if (t.pa.bf)
     hipLaunchKernelGGL((k_reduce1_catchup<D, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
@@ -321,6 +332,14 @@ extern "C" int ncf_reduce_batch_catchup(const ncf_reduce_list* list, float* scra
   if (max_n <= 0)
     return run_list("ncf_reduce_batch_catchup", list, scratch, scratch_floats, nullptr,
                     (hipStream_t)stream);
+  if ((pairs[0].param_dtype & NCF_ADAM_DECOUPLED) && dim > kDwFusedMaxDim) {
+    const int rc = run_list("ncf_reduce_batch_catchup", list, scratch, scratch_floats, nullptr,
+                            (hipStream_t)stream);
+    if (rc != NCF_OK) return rc;
+    return ncf_adam_pairs_catchup_lock_clock(pairs, npairs, dim, count, max_n, target_rel, 0,
+                                             clock, step_table, beta1, beta2, eps, weight_decay,
+                                             stream);
+  }
   if (list->count == 0)
     return ncf_adam_pairs_catchup_lock_clock(pairs, npairs, dim, count, max_n, target_rel, 0,
                                              clock, step_table, beta1, beta2, eps, weight_decay,

@@ -87,10 +87,26 @@ SWEEP_FORK = None
 GATHER_FORK_ROWS = 2560
 
 
+def adamw_step_scalars(lr, beta1, beta2, eps, weight_decay, first, count, out):
+    """The decoupled step table (include/ncf_hip.h) of steps first .. first + count - 1 into the
+    float32 array ``out`` (NCF_ADAMW_TABLE_STRIDE floats per step): the four floats of
+    ncf_adam_step_scalars, that step's decay (float)(1 - lr * weight_decay) — one fp32 rounding
+    of the double, as the library rounds its own per-step scalars — and zeros."""
+    S = _lib.ADAMW_TABLE_STRIDE
+    four = np.empty(4 * count, dtype=np.float32)
+    _lib.call("ncf_adam_step_scalars", lr, beta1, beta2, eps, first, count, four.ctypes.data)
+    rows = out[:S * count].reshape(count, S)
+    rows[:] = 0.0
+    rows[:, :4] = four.reshape(count, 4)
+    rows[:, 4] = np.float32(1.0 - float(lr) * float(weight_decay))
+    return out
+
+
 class DeferredTableAdam:
     def __init__(self, engine, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  sweep_every: int = 64, moments=None, clock=None, overlap_sweep=None,
-                 param_tables=None, rounding="nearest", rounding_seed=0):
+                 param_tables=None, rounding="nearest", rounding_seed=0,
+                 decoupled_weight_decay=False):
         self.engine = engine
         self._serial = next(_SERIAL)
         # clock (ncf_step_clock, device): every step-dependent value is read on the device, so
@@ -119,6 +135,18 @@ class DeferredTableAdam:
             raise ValueError("stochastic rounding needs the device step clock: only the "
                              "both-kinds entry points carry its seed")
         self.rounding_seed = int(rounding_seed) & 0xFFFFFFFF
+        # Decoupled weight decay (torch.optim.AdamW; NCF_ADAM_DECOUPLED, include/ncf_hip.h): the
+        # same schedule — an untouched row still shrinks by 1 - lr * wd every step and a row
+        # touched once keeps moving on its decaying exp_avg — with the other element update and
+        # the decoupled scalar table, whose per-step decay carries lr and wd of that step.
+        self.decoupled = bool(decoupled_weight_decay)
+        if self.decoupled and self.bf16:
+            raise ValueError("decoupled weight decay steps fp32 tables (no bf16 param_tables)")
+        if self.decoupled and clock is None:
+            raise ValueError("decoupled weight decay needs the device step clock: only the "
+                             "both-kinds entry points carry the flag")
+        # floats per step of the scalar table
+        self._stride = _lib.ADAMW_TABLE_STRIDE if self.decoupled else 4
         dev = self.tables["mf_user"].device
         self.state = moments or {k: {"exp_avg": torch.zeros_like(p), "exp_avg_sq": torch.zeros_like(p)}
                                  for k, p in self.params.items()}     # (fp32 moments)
@@ -184,11 +212,18 @@ class DeferredTableAdam:
                  engine.attn_tower_step(D, H, M, list(m.mlp_hidden_dims)))
         return "tower" if fused else "mlp_bwd"
 
-    # ---- per-step scalar table (index 4s .. 4s+3 = step s: gradient-step and zero-gradient-step
-    #      scalars, ncf_adam_step_scalars)
+    # ---- per-step scalar table (index S s .. S s + 3 = step s: gradient-step and zero-gradient-step
+    #      scalars, ncf_adam_step_scalars; S = self._stride: 4, or decoupled 8 with that step's
+    #      decay at S s + 4, adamw_step_scalars)
+    def _hp_key(self):
+        """What the filled scalars were computed from: lr, betas, eps — and, decoupled, the
+        weight decay, which lives in the table's per-step decay."""
+        b1, b2 = self.betas
+        return (self.lr, b1, b2, self.eps) + ((self.wd,) if self.decoupled else ())
+
     def _ensure(self, upto: int):
         b1, b2 = self.betas
-        hp = (self.lr, b1, b2, self.eps)
+        hp = self._hp_key()
         if upto <= self._filled and self._hp_filled == hp:
             return
         if self._hp_filled is None:
@@ -206,10 +241,14 @@ class DeferredTableAdam:
             last = max(upto, first) + SCALAR_PAD
         first = max(1, first)
         last = max(last, first)
-        host = np.empty(4 * (last - first + 1), dtype=np.float32)
-        _lib.call("ncf_adam_step_scalars", self.lr, b1, b2, self.eps, first, last - first + 1,
-                  host.ctypes.data)
-        need = 4 * (last + 1)
+        S = self._stride
+        host = np.empty(S * (last - first + 1), dtype=np.float32)
+        if self.decoupled:
+            adamw_step_scalars(self.lr, b1, b2, self.eps, self.wd, first, last - first + 1, host)
+        else:
+            _lib.call("ncf_adam_step_scalars", self.lr, b1, b2, self.eps, first,
+                      last - first + 1, host.ctypes.data)
+        need = S * (last + 1)
         if self._table.numel() < need:
             dev = self._table.device
             if self._table.numel():
@@ -229,7 +268,7 @@ class DeferredTableAdam:
             if self._table.numel():
                 grown[:self._table.numel()].copy_(self._table)
             self._table = grown
-        self._table[4 * first:4 * (last + 1)].copy_(torch.from_numpy(host))
+        self._table[S * first:S * (last + 1)].copy_(torch.from_numpy(host))
         self._filled, self._hp_filled = last, hp
 
     def set_hparams(self, lr, betas, eps, weight_decay):
@@ -238,7 +277,14 @@ class DeferredTableAdam:
         every replayed zero-gradient step, so rows still behind are first brought current with
         the old values (one full sweep, only when they change)."""
         betas = (float(betas[0]), float(betas[1]))
-        if (betas, float(eps), float(weight_decay)) != (self.betas, self.eps, self.wd):
+        if self.decoupled:
+            # (the decoupled decay is a per-step scalar of the table, as lr is: a change applies
+            # to the steps not yet taken, and rows behind replay the taken ones as they were)
+            if (betas, float(eps)) != (self.betas, self.eps):
+                self.sync()
+                self.betas, self.eps = betas, float(eps)
+            self.wd = float(weight_decay)
+        elif (betas, float(eps), float(weight_decay)) != (self.betas, self.eps, self.wd):
             self.sync()
             self.betas, self.eps, self.wd = betas, float(eps), float(weight_decay)
         self.lr = float(lr)
@@ -277,9 +323,16 @@ class DeferredTableAdam:
         return (ptr(self.tables[a]), ptr(s[a]["exp_avg"]), ptr(s[a]["exp_avg_sq"]),
                 ptr(self.tables[b]), ptr(s[b]["exp_avg"]), ptr(s[b]["exp_avg_sq"]))
 
+    def _no_row_lists(self):
+        if self.decoupled:
+            raise NotImplementedError("decoupled weight decay: the per-kind row-list entry "
+                                      "points (the row-sharded step's) have no decoupled form")
+
     # ---- row-list primitives (also used by the row-sharded step)
     def catchup_rows(self, kind, row_ids, count_dev, kind_index, max_n, st):
         """Bring the listed unique rows of `kind` current through step self.t."""
+        if max_n > 0:
+            self._no_row_lists()
         if self.clock is not None:
             if max_n > 0:
                 self._ensure(self.t + 1)
@@ -297,6 +350,7 @@ class DeferredTableAdam:
 
     def apply_rows(self, kind, row_ids, count_dev, kind_index, max_n, g_mf, g_mlp, st):
         """Step self.t + 1 on the listed rows (current through self.t) with their gradients."""
+        self._no_row_lists()
         step = self.t + 1
         self._ensure(step)
         if max_n <= 0:
@@ -419,6 +473,8 @@ class DeferredTableAdam:
             pr.stamp, pr.rows = ptr(self.stamp[kind]), self.stamp[kind].numel()
             pr.param_dtype = (_lib.DTYPE_BF16_SR if self.stochastic else
                               _lib.DTYPE_BF16 if self.bf16 else _lib.DTYPE_F32)
+            if self.decoupled:
+                pr.param_dtype |= _lib.ADAM_DECOUPLED
             # (the int32 field takes the seed's 32 bits as a signed value)
             pr.round_seed = self.rounding_seed - (1 << 32) * (self.rounding_seed >> 31) \
                 if self.stochastic else 0
@@ -607,8 +663,9 @@ class DeferredTableAdam:
     def _sweep(self, st):
         if self.clock is not None:
             self.flush(st)
-        if self.stochastic:
-            # ncf_adam_sweep_bf16 carries no seed: the rolling sweep with a period of 1 is every
+        if self.stochastic or self.decoupled:
+            # ncf_adam_sweep_bf16 carries no seed (and ncf_adam_sweep has no decoupled form): the
+            # rolling sweep with a period of 1 is every
             # row of both kinds brought to clock->t (= self.t between steps), the same replay
             self._ensure(self.t + 1)
             pairs = self.__dict__.get("_sweep_pairs") or self.__dict__.setdefault(

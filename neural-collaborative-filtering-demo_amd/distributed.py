@@ -336,6 +336,9 @@ class ShardedTrainStep:
 
     def __init__(self, ops, exchange: ShardExchange, ahead: Optional[bool] = None):
         self.ops, self.x = ops, exchange
+        if getattr(getattr(ops, "deferred", None), "decoupled", False):
+            raise NotImplementedError("the row-sharded step has no decoupled weight decay: its "
+                                      "owner-side apply implements coupled L2 only")
         self._pending = None      # [user_ids, item_ids, Plan, (recv, event) | None] planned ahead
         # send the next step's rows to their owners during this step (SHARD_AHEAD)
         self.ahead = ahead if ahead is not None else bool(SHARD_AHEAD)
@@ -545,7 +548,13 @@ class HipShardOps:
     """Per-rank work of the sharded step on the MI355X (HIP kernels through the C-ABI)."""
 
     def __init__(self, model, num_users: int, num_items: int, world: int, lr=1e-3,
-                 betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, sweep_every=None):
+                 betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, sweep_every=None,
+                 decoupled_weight_decay: bool = False):
+        if decoupled_weight_decay:
+            # (the owner-side apply, ncf_adam_pairs_apply_gsum_clock, has no decoupled form)
+            raise NotImplementedError("the row-sharded step implements torch.optim.Adam's "
+                                      "coupled weight decay only (decoupled_weight_decay: "
+                                      "FusedTrainStep or torch.optim.AdamW on one device)")
         sweep_every = SWEEP_EVERY if sweep_every is None else sweep_every
         from .deferred import DeferredTableAdam
         if world > _lib.SHARD_MAX_WORLD:

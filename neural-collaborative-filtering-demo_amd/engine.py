@@ -205,7 +205,14 @@ class Workspace:
         buffer (groups in flight at the same time need distinct ones)."""
         if not self.wgrads:
             return
-        descs = (_lib.WgradDesc * len(self.wgrads))()
+        # One descriptor array per (slot, count), kept for the workspace's lifetime and rewritten
+        # in place: a launch tape of this backward (tapes.py) holds the array by address, and a
+        # fresh array per call left it reading freed host memory on replay (seen at D = 16,
+        # n = 40: "ncf_wgrad_grouped: bad descriptor 0" once the block had been reused).
+        keep = self.__dict__.setdefault("_wg_descs", {})
+        descs = keep.get((slot, len(self.wgrads)))
+        if descs is None:
+            descs = keep[(slot, len(self.wgrads))] = (_lib.WgradDesc * len(self.wgrads))()
         for d, (dY, ldy, X, ldx, dW, ldw, m_out, k_in, n, dbias) in zip(descs, self.wgrads):
             d.dy, d.x, d.dw, d.dbias = ptr(dY), ptr(X), ptr(dW), ptr(dbias)
             d.ldy, d.ldx, d.ldw = ldy, ldx, ldw
@@ -1249,8 +1256,11 @@ class NCFEngine:
     def table_state_tensors(self):
         return self.table_params()
 
-    def adam_tables(self, hp_for, state_for, step: float, st):
-        """Dense-exact Adam over the four tables using the pending compact grads."""
+    def adam_tables(self, hp_for, state_for, step: float, st, decoupled: bool = False):
+        """Dense-exact Adam over the four tables using the pending compact grads
+        (``decoupled``: AdamW's decay rule, which these entry points take as a negative step)."""
+        if decoupled:
+            step = -step
         w = self.pending
         tb = self.table_params()
         for key, p in tb.items():

@@ -22,8 +22,12 @@ hooks bring lagging table rows current first, so the torch format stays exact.  
 parameters the fused step updated are taken out of the param groups for the duration of
 torch's own step (so torch's loop never sees them) and put back afterwards.
 
+``torch.optim.AdamW`` and ``Adam(decoupled_weight_decay=True)`` take the same path with decoupled
+decay (``_decoupled``; the flagged table pairs and flat calls, include/ncf_hip.h):
+an untouched row then shrinks by ``1 - lr * wd`` per step, still every row every step.
+
 ``SCHEDULE = "dense"`` keeps the dense per-step table sweep instead (A/B and tests).  Optimizers
-other than plain Adam (amsgrad, maximize, capturable, differentiable, tensor lr, other classes)
+other than these (amsgrad, maximize, capturable, differentiable, tensor lr, other classes)
 receive materialised dense table gradients and run unchanged.
 """
 import weakref
@@ -51,15 +55,25 @@ def register(model):
 
 
 def _is_plain_adam(opt):
-    if type(opt) is not torch.optim.Adam:
+    """Whether the fused step implements this optimizer: torch.optim.Adam (coupled L2) or
+    torch.optim.AdamW / Adam(decoupled_weight_decay=True) (decoupled: _decoupled), without
+    amsgrad / maximize / differentiable / capturable / a tensor lr."""
+    if type(opt) not in (torch.optim.Adam, torch.optim.AdamW):
         return False
     for g in opt.param_groups:
         if g.get("amsgrad") or g.get("maximize") or g.get("differentiable") or \
-                g.get("capturable") or g.get("decoupled_weight_decay", False):
+                g.get("capturable"):
             return False
         if isinstance(g["lr"], torch.Tensor):
             return False
     return True
+
+
+def _decoupled(opt, group):
+    """The decay rule of a param group: AdamW's (True) or Adam's coupled L2.  torch's AdamW is
+    Adam with decoupled_weight_decay=True in its groups; an AdamW of a release that keeps no
+    such key decays decoupled all the same."""
+    return bool(group.get("decoupled_weight_decay", type(opt) is torch.optim.AdamW))
 
 
 def _models_in(opt):
@@ -120,6 +134,8 @@ class _Binding:
         self.dense = eng.dense_params()
         self.flat_ptr = eng.flat.data_ptr()
         self.hp = _hp(group)
+        # the decay rule this binding is bound to (a group that changes it gets a new binding)
+        self.decoupled = _decoupled(opt, group)
         self.uniform = True          # every parameter so far stepped on the shared counter
         self.step_t = torch.tensor(0.0)
         self._step_np = self.step_t.numpy()   # (the same scalar: bumped without a torch op)
@@ -138,7 +154,8 @@ class _Binding:
         if SCHEDULE == "deferred" and model.mf_embedding_dim == model.mlp_embedding_dim:
             self.D = DeferredTableAdam(eng, lr, betas, eps, wd, SWEEP_EVERY,
                                        moments=self.moments, clock=self.clock,
-                                       overlap_sweep=deferred_mod.OVERLAP_SWEEP)
+                                       overlap_sweep=deferred_mod.OVERLAP_SWEEP,
+                                       decoupled_weight_decay=self.decoupled)
             eng.clock = self.clock
         self.adopt(opt)
 
@@ -194,6 +211,16 @@ class _Binding:
             eng.clock = None
         self.D = None
 
+    @property
+    def _rel1(self):
+        """step_rel = 1 of the flat clock forms, with this binding's decay rule (decoupled:
+        NCF_ADAM_DECOUPLED ORed in, include/ncf_hip.h)."""
+        return 1 | (_lib.ADAM_DECOUPLED if self.decoupled else 0)
+
+    def _step_arg(self, step):
+        """The ``step`` argument of the fixed-step forms: negative selects decoupled decay."""
+        return -float(step) if self.decoupled else float(step)
+
     def valid(self, model):
         return self.eng is model.engine and self.eng.flat is not None and \
             self.eng.flat.data_ptr() == self.flat_ptr and \
@@ -212,7 +239,7 @@ class _Binding:
             m = self.moments[k]
             _lib.call("ncf_adam_table_dense_grad", ptr(p), ptr(p.grad.contiguous()), ptr(m["exp_avg"]),
                       ptr(m["exp_avg_sq"]), p.numel(), lr, b1, b2, eps, wd,
-                      float(self.step + 1), st)
+                      self._step_arg(self.step + 1), st)
             stepped = True
         return stepped
 
@@ -270,8 +297,8 @@ class _Binding:
                 eng.pending = None
                 d.sweep_join()        # (the clock advance below changes the sweep's target)
                 _lib.call("ncf_adam_flat_clock_close", ptr(eng.flat), ptr(eng.flat_grad),
-                          ptr(self.m_flat), ptr(self.v_flat), eng.flat.numel(), ptr(d._table), 1,
-                          ptr(self.clock), b1, b2, eps, wd, self.base_seed, s_)
+                          ptr(self.m_flat), ptr(self.v_flat), eng.flat.numel(), ptr(d._table),
+                          self._rel1, ptr(self.clock), b1, b2, eps, wd, self.base_seed, s_)
             tp = eng.tapes
             if tp is None or not tp.step(w, run):
                 run()
@@ -287,7 +314,8 @@ class _Binding:
         elif w is not None:            # SCHEDULE == "dense": sweep every row of every table
             hpf = lambda p: (lr, b1, b2, eps, wd)  # noqa: E731
             key_of = {id(p): k for k, p in self.tables.items()}
-            eng.adam_tables(hpf, lambda p: self.moments[key_of[id(p)]], float(self.step + 1), st)
+            eng.adam_tables(hpf, lambda p: self.moments[key_of[id(p)]], float(self.step + 1), st,
+                            decoupled=self.decoupled)
         elif table_grads:
             self.step_tables_dense_grads(hp, st)
             if d is not None:
@@ -299,10 +327,10 @@ class _Binding:
             # the step's dense Adam + the clock advance in one launch (as FusedTrainStep)
             d.sweep_join()
             _lib.call("ncf_adam_flat_clock_close", ptr(eng.flat), ptr(eng.flat_grad),
-                      ptr(self.m_flat), ptr(self.v_flat), eng.flat.numel(), ptr(d._table), 1,
-                      ptr(self.clock), b1, b2, eps, wd, self.base_seed, st)
+                      ptr(self.m_flat), ptr(self.v_flat), eng.flat.numel(), ptr(d._table),
+                      self._rel1, ptr(self.clock), b1, b2, eps, wd, self.base_seed, st)
         else:
-            step = float(self.step + 1)
+            step = self._step_arg(self.step + 1)
             if all_dense and self.uniform:
                 _lib.call("ncf_adam_flat", ptr(eng.flat), ptr(eng.flat_grad), ptr(self.m_flat),
                           ptr(self.v_flat), eng.flat.numel(), lr, b1, b2, eps, wd, step, st)
@@ -342,6 +370,7 @@ def _bindings(opt):
     if b is None:
         b = opt.__dict__["_ncf_bind"] = {}
         opt.register_state_dict_pre_hook(_opt_state_dict_pre)
+        opt.register_state_dict_post_hook(_opt_state_dict_post)
         opt.register_load_state_dict_pre_hook(_opt_load_pre)
         opt.register_load_state_dict_post_hook(_opt_load_post)
     return b
@@ -350,6 +379,19 @@ def _bindings(opt):
 def _opt_state_dict_pre(opt):
     for b in list(opt.__dict__.get("_ncf_bind", {}).values()):
         b.sync()
+
+
+def _opt_state_dict_post(opt, state_dict):
+    """Every bound parameter shares one ``step`` tensor.  A stock torch optimizer that loads the
+    dict keeps a CPU ``step`` by reference and increments it once per parameter, so all but the
+    first would see a step count too high: each entry of the returned dict gets a ``step`` of
+    its own (the entries are copies; ``optimizer.state`` keeps the shared one)."""
+    state = state_dict["state"]
+    for k, s in list(state.items()):
+        st = s.get("step")
+        if torch.is_tensor(st):
+            state[k] = dict(s, step=st.clone())
+    return state_dict
 
 
 def _opt_load_pre(opt, state_dict):
@@ -412,10 +454,14 @@ def _pre_hook(opt, args, kwargs):
     hidden = None
     for m in models:
         b = binds.get(id(m))
-        if b is None or not b.valid(m):
+        group = gmap[id(m.engine.table_params()["mf_user"])]
+        # (a binding is bound to one decay rule: a group that switched between coupled and
+        # decoupled decay detaches it — every row brought current under the old rule — and a
+        # new one adopts the optimizer's state)
+        if b is None or not b.valid(m) or b.decoupled != _decoupled(opt, group):
             if b is not None:
                 b.detach()
-            b = binds[id(m)] = _Binding(m, opt, gmap[id(m.engine.table_params()["mf_user"])])
+            b = binds[id(m)] = _Binding(m, opt, group)
         if b.run(opt, gmap):
             hidden = b._all_ids if hidden is None else hidden | b._all_ids
     if hidden:

@@ -21,6 +21,11 @@ was recorded in (``_pre`` keys) and the buffers it names are the same (``_signat
 state the replayed code would have left is then set as that code sets it (``_post``).  Anything
 else -- gradient accumulation, a frozen table, an lr change that moves the scalar table, an
 instrumented run -- takes the eager path for that phase.  ENABLED = False turns tapes off.
+A tape holds whichever C-ABI calls the eager code made, so the decoupled-weight-decay step
+(``torch.optim.AdamW``: the same entry points with the flagged table pairs, and
+``ncf_adam_flat_clock_close`` with the flag in ``step_rel``) is recorded and replayed like the
+coupled one; its weight decay lives in the scalar table (``_horizon`` refills it) and, being a launch argument too, in the
+signature.
 """
 
 import torch
@@ -82,8 +87,7 @@ class StepTapes:
         d._ensure(t + 1)); refilled in place from the host when needed, outside any tape.
         False when that moved the table (its address is in the tapes)."""
         d = self.eng.deferred
-        b1, b2 = d.betas
-        if d._filled >= d.t + 2 and d._hp_filled == (d.lr, b1, b2, d.eps):
+        if d._filled >= d.t + 2 and d._hp_filled == d._hp_key():
             return True
         at = d._table.data_ptr()
         d._ensure(d.t + 2)
@@ -279,8 +283,7 @@ class SegmentTapes:
     def horizon(d):
         """The scalar table covers the step (outside any tape; an address change shows in the
         caller's signature)."""
-        b1, b2 = d.betas
-        if d._filled < d.t + 2 or d._hp_filled != (d.lr, b1, b2, d.eps):
+        if d._filled < d.t + 2 or d._hp_filled != d._hp_key():
             d._ensure(d.t + 2)
 
     def run(self, key, sig, pre, ranges, scalars, fn, post) -> bool:

@@ -123,9 +123,19 @@ class FusedTrainStep:
                  clock: Optional[bool] = None, warmup: int = 2, concurrent: Optional[bool] = None,
                  overlap_sweep: Optional[bool] = None, table_dtype: torch.dtype = torch.float32,
                  max_grad_norm: Optional[float] = None, table_rounding: str = "nearest",
-                 rounding_seed: Optional[int] = None):
+                 rounding_seed: Optional[int] = None, decoupled_weight_decay: bool = False):
         self.model = model
         self.deferred = None
+        # Decoupled weight decay (torch.optim.AdamW's rule): fp32 tables only
+        # (refused before anything of the model is touched)
+        self.decoupled = bool(decoupled_weight_decay)
+        if self.decoupled and table_dtype == torch.bfloat16:
+            raise ValueError("decoupled_weight_decay=True steps fp32 tables "
+                             "(table_dtype=torch.float32)")
+        if self.decoupled and deferred and clock is False and \
+                model.mf_embedding_dim == model.mlp_embedding_dim:
+            raise ValueError("decoupled_weight_decay=True with the deferred table Adam needs "
+                             "the step clock (clock not False)")
         # global gradient-norm clipping (clip.py): the 2-norm over the four compact
         # table gradients and the flat dense buffer, scaled in place before any Adam reads them
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
@@ -208,7 +218,8 @@ class FusedTrainStep:
                                               overlap_sweep=overlap_sweep and self.clock is not None,
                                               param_tables=self.tables_lp,
                                               rounding=table_rounding,
-                                              rounding_seed=self.rounding_seed or 0)
+                                              rounding_seed=self.rounding_seed or 0,
+                                              decoupled_weight_decay=self.decoupled)
         self.warmup = warmup
         # independent kernels on side streams.  Off by default: measured slower on MI355X, eager
         # (0.63 vs 0.54 ms) and captured (0.71 vs 0.58 ms) — a cross-queue dependency costs more
@@ -296,18 +307,22 @@ class FusedTrainStep:
         else:
             hp = lambda p: (self.lr, b1, b2, self.eps, self.wd)  # noqa: E731
             key_of = {id(p): k for k, p in self.tables.items()}
-            eng.adam_tables(hp, lambda p: self.state[key_of[id(p)]], float(self.step_count + 1), st)
+            eng.adam_tables(hp, lambda p: self.state[key_of[id(p)]], float(self.step_count + 1), st,
+                            decoupled=self.decoupled)
         eng.join_reductions()
+        # decoupled decay (include/ncf_hip.h): a flag in step_rel, a negative step
+        rel1 = 1 | (_lib.ADAM_DECOUPLED if self.decoupled else 0)
+        sgn = -1.0 if self.decoupled else 1.0
         if self.clock is not None:
             self.deferred.sweep_join()       # (the clock advance below changes its target)
             _lib.call("ncf_adam_flat_clock_close", ptr(eng.flat), ptr(eng.flat_grad),
                       ptr(self.m_flat), ptr(self.v_flat), eng.flat.numel(),
-                      ptr(self.deferred._table), 1, ptr(self.clock), b1, b2, self.eps, self.wd,
+                      ptr(self.deferred._table), rel1, ptr(self.clock), b1, b2, self.eps, self.wd,
                       self.base_seed, st)
         else:
             _lib.call("ncf_adam_flat", ptr(eng.flat), ptr(eng.flat_grad), ptr(self.m_flat),
                       ptr(self.v_flat), eng.flat.numel(), self.lr, b1, b2, self.eps, self.wd,
-                      float(self.step_count + 1), st)
+                      sgn * float(self.step_count + 1), st)
         return w
 
     def _tables_done(self):
@@ -562,7 +577,8 @@ class FusedTrainStep:
                     p.copy_(self.tables_lp[k])
 
     def load_optimizer_state(self, state_dict):
-        """Resume from a ``torch.optim.Adam(model.parameters())`` state_dict (what
+        """Resume from a ``torch.optim.Adam(model.parameters())`` state_dict (or, with
+        ``decoupled_weight_decay=True``, a ``torch.optim.AdamW`` one: the same keys) (what
         export_optimizer_state / checkpoint.save_checkpoint and the reference trainer write):
         moments and step of every trained parameter; the deferred schedule restarts with every
         row current at that step."""
@@ -631,8 +647,15 @@ class ModelTrainer:
         self.num_gpus = num_gpus
         self.negative_samples = config.get("negative_samples", 4)
         weight_decay = float(config.get("weight_decay", 1e-5))
-        self.optimizer = torch.optim.Adam(self.model.parameters(), lr=config["learning_rate"],
-                                          weight_decay=weight_decay)
+        # config["optimizer"]: "adam" (the default and the reference's, trainer.py:71-75) or
+        # "adamw": torch.optim.AdamW with the same lr / weight_decay (decoupled decay; the
+        # fused step implements both, optim.py)
+        kind = str(config.get("optimizer", "adam")).lower()
+        if kind not in ("adam", "adamw"):
+            raise ValueError(f"config['optimizer'] must be 'adam' or 'adamw', got {kind!r}")
+        opt_cls = torch.optim.AdamW if kind == "adamw" else torch.optim.Adam
+        self.optimizer = opt_cls(self.model.parameters(), lr=config["learning_rate"],
+                                 weight_decay=weight_decay)
         self.criterion = nn.BCELoss().to(self.device)
         self.model = self.model.to(self.device)
 
