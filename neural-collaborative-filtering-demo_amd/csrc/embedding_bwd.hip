@@ -21,6 +21,7 @@
 // Deterministic: every sum has a fixed order.
 #include "segments.h"
 #include "adam_math.h"
+#include "reduce_dev.h"   // stage1_sum: the chunk rows of the deferred LayerNorm gradients
 
 using namespace ncf_seg;
 
@@ -208,7 +209,32 @@ __global__ __launch_bounds__(64 * kPW) void k_piece_reduce_ln(
   }
 }
 
-// G[c] += extra pieces of segment c (in piece order); L lanes per segment
+// Stage 1 of the deferred dgamma/dbeta reduction when it needs two (P = 2 nbr partial rows >
+// NCF_REDUCE_ONE_STAGE): block e of ncf_cdiv(4 D, 256) * chunks sums one chunk of kPB partial rows
+// of `part` over 256 columns into row y of `rows` ([chunks][4 D]).  stage1_sum and the wave
+// combine of reduce1_body's vec form, column by column what ncf_reduce_batch's stage 1 wrote for
+// the four descriptors {part + q D, P, 4 D, D}: the same chunk rows, bit for bit.
+template <int D>
+__device__ __forceinline__ void ln_stage1_block(const float* __restrict__ part,
+                                                float* __restrict__ rows, int P, uint32_t e,
+                                                float4 (*red)[64]) {
+  constexpr int64_t W = 4 * D;
+  constexpr uint32_t gx = (uint32_t)((W + 255) / 256);
+  const int y = (int)(e / gx);
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t i = ((int64_t)(e % gx) * 64 + l) * 4;
+  const int pb = y * ncf_reduce::kPB, pe = min(P, pb + ncf_reduce::kPB);
+  float4 s = ncf_reduce::zero<float4>();
+  if (i < W) s = ncf_reduce::stage1_sum<float4>(part, W, i, pb, pe, w);
+  red[w][l] = s;
+  __syncthreads();
+  if (w == 0 && i < W)
+    *(float4*)(rows + (int64_t)y * W + i) = (red[0][l] + red[1][l]) + (red[2][l] + red[3][l]);
+}
+
+// G[c] += extra pieces of segment c (in piece order); L lanes per segment: blocks [nst, nst + fbx)
+// of either kind.  The first nst blocks (x, over both kinds: e = 2 x + kind < ln_blocks) are the
+// stage 1 of the deferred LayerNorm gradients (ln_stage1_block; none unless piece_reduce asks).
 template <int D, bool BF = false>
 __global__ __launch_bounds__(256) void k_piece_fixup(
     const uint32_t* __restrict__ fpiece0, const uint32_t* __restrict__ fpiece1,
@@ -216,18 +242,26 @@ __global__ __launch_bounds__(256) void k_piece_fixup(
     const float* __restrict__ xp1, float* __restrict__ G_mf0, float* __restrict__ G_mlp0,
     float* __restrict__ G_mf1, float* __restrict__ G_mlp1, const int32_t* __restrict__ omap0,
     const int32_t* __restrict__ omap1, int64_t ldo, const int64_t* __restrict__ uniq0,
-    const int64_t* __restrict__ uniq1, const ApplyArgs ap) {
+    const int64_t* __restrict__ uniq1, const ApplyArgs ap, const float* __restrict__ ln_part,
+    float* __restrict__ ln_rows, int ln_P, uint32_t ln_blocks, uint32_t nst) {
   constexpr int L = D / 4;
   const int kind = blockIdx.y;
+  if (blockIdx.x < nst) {   // (block-uniform)
+    __shared__ float4 red[4][64];
+    const uint32_t e = 2 * blockIdx.x + kind;
+    if (e < ln_blocks) ln_stage1_block<D>(ln_part, ln_rows, ln_P, e, red);
+    return;
+  }
+  const uint32_t fbx = gridDim.x - nst;
   const int32_t* omap = kind ? omap1 : omap0;
   const uint32_t* fpiece = kind ? fpiece1 : fpiece0;
   const float* xp = kind ? xp1 : xp0;
   float* Gmf = kind ? G_mf1 : G_mf0;
   float* Gml = kind ? G_mlp1 : G_mlp0;
   const int64_t U = totals[kind];
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t t = (int64_t)(blockIdx.x - nst) * blockDim.x + threadIdx.x;
   const int col = (int)(t % L) * 4;
-  for (int64_t c = t / L; c < U; c += (int64_t)gridDim.x * blockDim.x / L) {
+  for (int64_t c = t / L; c < U; c += (int64_t)fbx * blockDim.x / L) {
     const uint32_t f0 = fpiece[c], f1 = fpiece[c + 1];
     if (f1 - f0 <= 1) continue;
     const int64_t orow = (omap ? (int64_t)omap[c] : c) * ldo;
@@ -294,20 +328,31 @@ int piece_reduce(const WS& w, int64_t n, const uint32_t* sv0, const uint32_t* sv
   NCF_CHECK_LAUNCH("ncf_embedding_bwd(piece_reduce)");
   constexpr int L = D / 4;
   const int64_t fb = ncf_cdiv(n * L, 256);
-  const dim3 fgrid((unsigned)(fb > 2048 ? 2048 : (fb < 1 ? 1 : fb)), 2);
+  // Deferred dgamma/dbeta with more partial rows than one stage takes: their stage 1 rides in
+  // the fix-up launch (the partials are final when k_piece_reduce_ln ends) and the list gets the
+  // chunk rows as single-stage reductions — the second stage of ncf_reduce_batch restated, so the
+  // step's tail needs no stage-2 launch.  The chunk rows live in w.red_scratch, which nothing
+  // else writes on this path: they stay valid until the next call on this workspace (as w.part
+  // does), so the deferred list must run before it.
+  const int P = 2 * w.nbr;
+  const int chunks = defer && P > NCF_REDUCE_ONE_STAGE ? (P + NCF_REDUCE_PB - 1) / NCF_REDUCE_PB : 0;
+  const uint32_t ln_blocks = (uint32_t)chunks * (uint32_t)((4 * D + 255) / 256);
+  const uint32_t nst = (ln_blocks + 1) / 2;
+  const dim3 fgrid((unsigned)(fb > 2048 ? 2048 : (fb < 1 ? 1 : fb)) + nst, 2);
   if (bf)
     hipLaunchKernelGGL((k_piece_fixup<D, true>), fgrid, dim3(256), 0, st, w.fpiece0, w.fpiece1,
                        w.totals, w.xp0, w.xp1, Gmf0, Gml0, Gmf1, Gml1, omap0, omap1, ldo, uniq0,
-                       uniq1, ap);
+                       uniq1, ap, (const float*)w.part, w.red_scratch, P, ln_blocks, nst);
   else
     hipLaunchKernelGGL((k_piece_fixup<D, false>), fgrid, dim3(256), 0, st, w.fpiece0, w.fpiece1,
                        w.totals, w.xp0, w.xp1, Gmf0, Gml0, Gmf1, Gml1, omap0, omap1, ldo, uniq0,
-                       uniq1, ap);
+                       uniq1, ap, (const float*)w.part, w.red_scratch, P, ln_blocks, nst);
   NCF_CHECK_LAUNCH("ncf_embedding_bwd(fixup)");
   if (defer) {
     float* const outs[4] = {dgm, dbm, dgl, dbl};
     for (int q = 0; q < 4; ++q) {
-      const int rc = ncf_defer(defer, w.part + q * D, 2 * w.nbr, 4 * D, D, outs[q], 0, D, D);
+      const int rc = chunks ? ncf_defer(defer, w.red_scratch + q * D, chunks, 4 * D, D, outs[q], 0, D, D)
+                            : ncf_defer(defer, w.part + q * D, P, 4 * D, D, outs[q], 0, D, D);
       if (rc) return rc;
     }
     return NCF_OK;
