@@ -22,15 +22,19 @@ using namespace ncf_adam;
 namespace {
 
 
-// DW (here and below): decoupled weight decay, a compile-time choice (step1 / step0 / step4,
-// adam_math.h); dk = the step's decay, not read by the coupled instantiations.  The fixed-step
-// kernels have no step table to take it from: scalars_dw puts it in the scalars' wd slot, which
-// the decoupled element update does not use (the kernel arguments keep their layout).
-template <int D, bool BF = false, bool DW = false>
+// V (here and below): the rows' variant (Rows, adam_math.h), BF / DW its properties.  DW:
+// decoupled weight decay, a compile-time choice (step1 / step0 / step4, adam_math.h); dk = the
+// step's decay, not read by the coupled instantiations.  The fixed-step kernels have no step
+// table to take it from: scalars_dw puts it in the scalars' wd slot, which the decoupled element
+// update does not use (the kernel arguments keep their layout).
+// (fp32, bf16 and decoupled rows: the dense schedule has no stochastic rounding)
+template <int D, Rows V>
 __global__ __launch_bounds__(256) void k_adam_table(float* __restrict__ p, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t rows,
                                                     const int32_t* __restrict__ slot,
                                                     const float* __restrict__ G, AdamScalars s) {
+  static_assert(!RowTraits<V>::SR, "k_adam_table rounds bf16 rows to nearest even only");
+  constexpr bool BF = RowTraits<V>::BF, DW = RowTraits<V>::DW;
   const float dk = DW ? s.wd : 1.f;   // (scalars_dw: the step's decay rides in the wd slot)
   const int64_t n4 = rows * (D / 4);
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4;
@@ -125,10 +129,11 @@ __global__ __launch_bounds__(256) void k_adam_catchup(TablePtrs t, const int64_t
 }
 
 // every row of the table caught up to `target` (materialise)
-template <int D, bool BF = false>
+template <int D, Rows V>
 __global__ __launch_bounds__(256) void k_adam_sweep(TablePtrs t, int64_t row0, int64_t rows,
                                                     int32_t* __restrict__ stamp, int32_t target,
                                                     const float* __restrict__ table, AdamScalars s) {
+  static_assert(V == Rows::F32 || V == Rows::BF16, "k_adam_sweep: coupled table, no round seed");
   constexpr int L = Replay<D>::LPR;   // lanes per row
   const int64_t n = rows * L;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n;
@@ -136,7 +141,7 @@ __global__ __launch_bounds__(256) void k_adam_sweep(TablePtrs t, int64_t row0, i
     const int64_t row = row0 + e / L;
     const int sub = (int)(e % L);
     const int32_t from = stamp[row];
-    catch_up_row<D, BF>(t, row, sub, from, target, table, s);
+    catch_up_row<D, V>(t, row, sub, from, target, table, s);
     // all L lanes of the row read stamp before this store: they share one wave-instruction
     if (sub == 0 && from < target) stamp[row] = target;
   }
@@ -205,7 +210,7 @@ __global__ __launch_bounds__(256) void k_adam_flat_clock(float* __restrict__ p,
                                                          int32_t step_rel,
                                                          const ncf_step_clock* __restrict__ clock,
                                                          AdamScalars s) {
-  constexpr int TS = StepTable<DW>::S;
+  constexpr int TS = step_stride(DW);
   const int32_t step = clock->t + step_rel;
   const float ns = table[TS * step], bc = table[TS * step + 1];
   const float dk = DW ? table[TS * step + 4] : 1.f;
@@ -221,14 +226,14 @@ __global__ __launch_bounds__(256) void k_adam_flat_clock(float* __restrict__ p,
 
 // ---- both id kinds per launch (blockIdx.y = kind; PairArgs and the catch-up's body:
 // adam_catchup_dev.h)
-template <int D, bool BF = false, bool SR = false, bool DW = false>
+template <int D, Rows V>
 __global__ __launch_bounds__(256) void k_pairs_catchup(const PairArgs a, const uint32_t* __restrict__ count,
                                                        int64_t max_n, int32_t target_rel,
                                                        const ncf_step_clock* __restrict__ clock,
                                                        const float* __restrict__ table,
                                                        AdamScalars s, int lock) {
-  pairs_catchup_body<D, BF, SR, DW>(a, blockIdx.y, blockIdx.x, count, max_n, target_rel, clock, table, s,
-                            lock);
+  pairs_catchup_body<D, V>(a, blockIdx.y, blockIdx.x, count, max_n, target_rel, clock, table, s,
+                           lock);
 }
 
 // Claim form of the pair catch-up, with no dedup before it: one row-group of lanes per
@@ -238,7 +243,7 @@ __global__ __launch_bounds__(256) void k_pairs_catchup(const PairArgs a, const u
 // backward needs can run on another stream beside the forward.  Locked rows (stamp = t |
 // NCF_STAMP_LOCK) compare above any target and are left alone.  Out-of-range ids are skipped
 // (the gather flags them).
-template <int D, bool BF = false, bool SR = false, bool DW = false>
+template <int D, Rows V>
 __global__ __launch_bounds__(256) void k_pairs_catchup_claim(const PairArgs a,
                                                              const int64_t* __restrict__ ids0,
                                                              const int64_t* __restrict__ ids1,
@@ -258,14 +263,15 @@ __global__ __launch_bounds__(256) void k_pairs_catchup_claim(const PairArgs a,
   int32_t from = target;
   if (sub == 0) from = atomicMax(&a.stamp[k][row], target);
   from = __shfl(from, (int)(threadIdx.x & 63) - sub, 64);   // the claim of this row's lane group
-  catch_up_row<D, BF, SR, DW>(a.t[k], row, sub, from, target, table, s, a.seed, k);
+  catch_up_row<D, V>(a.t[k], row, sub, from, target, table, s, a.seed, k);
 }
 
-template <int D, bool BF = false, bool SR = false, bool DW = false>
+template <int D, Rows V>
 __global__ __launch_bounds__(256) void k_pairs_apply(const PairArgs a, const uint32_t* __restrict__ count,
                                                      int64_t max_n, int32_t step_rel,
                                                      const ncf_step_clock* __restrict__ clock,
                                                      const float* __restrict__ table, AdamScalars s) {
+  constexpr bool BF = RowTraits<V>::BF, SR = RowTraits<V>::SR, DW = RowTraits<V>::DW;
   constexpr int L = D / 4;
   const int k = blockIdx.y;
   const int64_t tt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -276,7 +282,7 @@ __global__ __launch_bounds__(256) void k_pairs_apply(const PairArgs a, const uin
   const TablePtrs& t = a.t[k];
   const int64_t row = a.ids[k][c];
   const int64_t o = row * D + sub * 4;
-  constexpr int TS = StepTable<DW>::S;
+  constexpr int TS = RowTraits<V>::TS;
   const float ns = table[TS * step], bc = table[TS * step + 1];
   const float dk = DW ? table[TS * step + 4] : 1.f;
   // every load of both tables before any store: the compiler cannot know the two tables' rows
@@ -345,7 +351,7 @@ __global__ __launch_bounds__(256) void k_pairs_apply_gsum(const PairArgs a, cons
 }
 
 // part `part` of `nparts` (consecutive row ranges) of the slice of step clock->t + step_rel
-template <int D, bool BF = false, bool SR = false, bool DW = false>
+template <int D, Rows V>
 __global__ __launch_bounds__(256) void k_pairs_sweep(const PairArgs a, int32_t every,
                                                      int32_t step_rel,
                                                      const ncf_step_clock* __restrict__ clock,
@@ -367,7 +373,7 @@ __global__ __launch_bounds__(256) void k_pairs_sweep(const PairArgs a, int32_t e
     const int64_t row = row0 + e / L;
     const int sub = (int)(e % L);
     const int32_t from = stamp[row];
-    catch_up_row<D, BF, SR, DW>(a.t[k], row, sub, from, target, table, s, a.seed, k);
+    catch_up_row<D, V>(a.t[k], row, sub, from, target, table, s, a.seed, k);
     if (sub == 0 && from < target) stamp[row] = target;
   }
 }
@@ -396,7 +402,7 @@ __global__ __launch_bounds__(256) void k_adam_flat_close(float* __restrict__ p,
                                                          const float* __restrict__ table,
                                                          int32_t step_rel, ncf_step_clock* clock,
                                                          uint64_t base_seed, AdamScalars s) {
-  constexpr int TS = StepTable<DW>::S;
+  constexpr int TS = step_stride(DW);
   const int32_t step = clock->t + step_rel;
   const float ns = table[TS * step], bc = table[TS * step + 1];
   const float dk = DW ? table[TS * step + 4] : 1.f;
@@ -442,15 +448,28 @@ int grid_for(int64_t work) {
 
 template <int D>
 int table_d(float* p, float* m, float* v, int64_t rows, const int32_t* slot, const float* G,
-            const AdamScalars& s, hipStream_t st, bool bf = false, bool dw = false) {
-  if (dw)
-    hipLaunchKernelGGL((k_adam_table<D, false, true>), dim3(grid_for(rows * (D / 4))), dim3(256), 0, st, p, m, v, rows, slot, G, s);
-  else if (bf)
-    hipLaunchKernelGGL((k_adam_table<D, true>), dim3(grid_for(rows * (D / 4))), dim3(256), 0, st, p, m, v, rows, slot, G, s);
-  else
-    hipLaunchKernelGGL((k_adam_table<D, false>), dim3(grid_for(rows * (D / 4))), dim3(256), 0, st, p, m, v, rows, slot, G, s);
-  NCF_CHECK_LAUNCH("ncf_adam_table");
+            const AdamScalars& s, hipStream_t st, Rows rows_v, const char* who) {
+  for_rows<Rows::F32, Rows::BF16, Rows::F32_DW>(rows_v, [&](auto V) {
+    hipLaunchKernelGGL((k_adam_table<D, V()>), dim3(grid_for(rows * (D / 4))), dim3(256), 0, st,
+                       p, m, v, rows, slot, G, s);
+  });
+  NCF_CHECK_LAUNCH(who);
   return NCF_OK;
+}
+
+// The flat entries' encodings of decoupled weight decay (torch.optim.AdamW; ABI,
+// include/ncf_hip.h), each taken off its argument here and nowhere else: a NEGATIVE `step` is
+// step -step under it, and so is NCF_ADAM_DECOUPLED ORed into a (non-negative) step_rel.
+bool take_dw(double& step) {
+  const bool dw = step < 0;
+  if (dw) step = -step;
+  return dw;
+}
+
+bool take_dw(int32_t& step_rel) {
+  const bool dw = step_rel >= 0 && (step_rel & NCF_ADAM_DECOUPLED);
+  if (dw) step_rel &= ~NCF_ADAM_DECOUPLED;
+  return dw;
 }
 
 // the scalars of a decoupled step at a host-given step: no wd term in the element update (k1 =
@@ -462,38 +481,27 @@ AdamScalars scalars_dw(double lr, double beta1, double beta2, double eps, double
   return s;
 }
 
-int flat_step(const char* who, bool dw, float* param, const float* grad, float* exp_avg,
-              float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2, double eps,
-              double weight_decay, double step, void* stream) {
-  NCF_CHECK_ARG(n >= 0 && step >= 1, "%s: bad args", who);
-  if (n == 0) return NCF_OK;
-  NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq, "%s: null pointer", who);
-  if (dw)
-    hipLaunchKernelGGL(k_adam_flat<true>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
-                       param, grad, exp_avg, exp_avg_sq, n,
-                       scalars_dw(lr, beta1, beta2, eps, weight_decay, step));
-  else
-    hipLaunchKernelGGL(k_adam_flat<false>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
-                       param, grad, exp_avg, exp_avg_sq, n,
-                       make_scalars(lr, beta1, beta2, eps, weight_decay, step));
-  NCF_CHECK_LAUNCH(who);
-  return NCF_OK;
+AdamScalars step_scalars(bool dw, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, double step) {
+  return dw ? scalars_dw(lr, beta1, beta2, eps, weight_decay, step)
+            : make_scalars(lr, beta1, beta2, eps, weight_decay, step);
 }
 
-int dense_grad_step(const char* who, bool dw, float* param, const float* grad, float* exp_avg,
-                    float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
-                    double eps, double weight_decay, double step, void* stream) {
+// one step of a flat buffer at a host-given step (ncf_adam_flat, ncf_adam_table_dense_grad):
+// `coupled` / `decoupled` are the entry's kernel under the two decay rules
+using FlatKernel = void (*)(float*, const float*, float*, float*, int64_t, AdamScalars);
+
+int flat_step(const char* who, FlatKernel coupled, FlatKernel decoupled, float* param,
+              const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr,
+              double beta1, double beta2, double eps, double weight_decay, double step,
+              void* stream) {
+  const bool dw = take_dw(step);
   NCF_CHECK_ARG(n >= 0 && step >= 1, "%s: bad args", who);
   if (n == 0) return NCF_OK;
   NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq, "%s: null pointer", who);
-  if (dw)
-    hipLaunchKernelGGL(k_adam_table_dense_grad<true>, dim3(grid_for(n)), dim3(256), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
-                       scalars_dw(lr, beta1, beta2, eps, weight_decay, step));
-  else
-    hipLaunchKernelGGL(k_adam_table_dense_grad<false>, dim3(grid_for(n)), dim3(256), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
-                       make_scalars(lr, beta1, beta2, eps, weight_decay, step));
+  hipLaunchKernelGGL(dw ? decoupled : coupled, dim3(grid_for(n)), dim3(256), 0,
+                     (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
+                     step_scalars(dw, lr, beta1, beta2, eps, weight_decay, step));
   NCF_CHECK_LAUNCH(who);
   return NCF_OK;
 }
@@ -519,31 +527,30 @@ extern "C" int ncf_adam_table(float* param, float* exp_avg, float* exp_avg_sq, i
                               int64_t dim, const int32_t* slot, const float* grad_compact,
                               double lr, double beta1, double beta2, double eps,
                               double weight_decay, double step, void* stream) {
-  const bool dw = step < 0;
-  if (dw) step = -step;
+  const bool dw = take_dw(step);
   NCF_CHECK_ARG(rows >= 0 && step >= 1, "ncf_adam_table: bad args");
   if (rows == 0) return NCF_OK;
   NCF_CHECK_ARG(param && exp_avg && exp_avg_sq, "ncf_adam_table: null pointer");
-  const AdamScalars s = dw ? scalars_dw(lr, beta1, beta2, eps, weight_decay, step)
-                           : make_scalars(lr, beta1, beta2, eps, weight_decay, step);
-  NCF_DISPATCH_DIM(dim, table_d, param, exp_avg, exp_avg_sq, rows, slot, grad_compact, s,
-                   (hipStream_t)stream, false, dw);
+  NCF_DISPATCH_DIM(dim, table_d, param, exp_avg, exp_avg_sq, rows, slot, grad_compact,
+                   step_scalars(dw, lr, beta1, beta2, eps, weight_decay, step),
+                   (hipStream_t)stream, dw ? Rows::F32_DW : Rows::F32, "ncf_adam_table");
 }
 
 // Adam over a flat fp32 buffer (the dense parameters, packed contiguously by the host).
 extern "C" int ncf_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                              int64_t n, double lr, double beta1, double beta2, double eps,
                              double weight_decay, double step, void* stream) {
-  return flat_step("ncf_adam_flat", step < 0, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
-                   beta2, eps, weight_decay, step < 0 ? -step : step, stream);
+  return flat_step("ncf_adam_flat", k_adam_flat<false>, k_adam_flat<true>, param, grad, exp_avg,
+                   exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, stream);
 }
 
 extern "C" int ncf_adam_table_dense_grad(float* param, const float* grad, float* exp_avg,
                                          float* exp_avg_sq, int64_t n, double lr, double beta1,
                                          double beta2, double eps, double weight_decay,
                                          double step, void* stream) {
-  return dense_grad_step("ncf_adam_table_dense_grad", step < 0, param, grad, exp_avg, exp_avg_sq,
-                         n, lr, beta1, beta2, eps, weight_decay, step < 0 ? -step : step, stream);
+  return flat_step("ncf_adam_table_dense_grad", k_adam_table_dense_grad<false>,
+                   k_adam_table_dense_grad<true>, param, grad, exp_avg, exp_avg_sq, n, lr, beta1,
+                   beta2, eps, weight_decay, step, stream);
 }
 
 extern "C" int ncf_scatter_compact_rows(float* dense_grad, int64_t dim, const int64_t* uniq,
@@ -559,21 +566,49 @@ namespace {
 template <int D>
 int catchup_d(TablePtrs t, const int64_t* ids, const uint32_t* count, int kind, int64_t max_n,
               int32_t* stamp, int32_t target, const float* table, AdamScalars s,
-              const ncf_step_clock* clock, hipStream_t st) {
+              const ncf_step_clock* clock, hipStream_t st, const char* who) {
   hipLaunchKernelGGL(k_adam_catchup<D>, dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256)), dim3(256), 0, st, t,
                      ids, count, kind, max_n, stamp, target, table, s, clock);
-  NCF_CHECK_LAUNCH("ncf_adam_rows_catchup");
+  NCF_CHECK_LAUNCH(who);
   return NCF_OK;
 }
 
 template <int D>
 int apply_d(TablePtrs t, const int64_t* ids, const uint32_t* count, int kind, int64_t max_n,
             int32_t* stamp, int32_t step, const float* table, AdamScalars s,
-            const ncf_step_clock* clock, hipStream_t st) {
+            const ncf_step_clock* clock, hipStream_t st, const char* who) {
   hipLaunchKernelGGL(k_adam_apply<D>, dim3(ncf_cdiv(max_n * (D / 4), 256)), dim3(256), 0, st, t,
                      ids, count, kind, max_n, stamp, step, table, s, clock);
-  NCF_CHECK_LAUNCH("ncf_adam_rows_apply");
+  NCF_CHECK_LAUNCH(who);
   return NCF_OK;
+}
+
+// the single-table catch-up and apply of listed rows, at a host-given step (clock == NULL) or at
+// clock->t + step
+int rows_catchup(const char* who, float* p0, float* m0, float* v0, float* p1, float* m1,
+                 float* v1, int64_t dim, const int64_t* row_ids, const uint32_t* count, int kind,
+                 int64_t max_n, int32_t* stamp, int32_t target, const ncf_step_clock* clock,
+                 const float* step_table, double beta1, double beta2, double eps,
+                 double weight_decay, void* stream) {
+  if (max_n <= 0) return NCF_OK;
+  NCF_CHECK_ARG(p0 && m0 && v0 && row_ids && stamp && step_table, "%s: null", who);
+  TablePtrs t{p0, m0, v0, p1, m1, v1, nullptr, nullptr};
+  NCF_DISPATCH_DIM(dim, catchup_d, t, row_ids, count, kind, max_n, stamp, target, step_table,
+                   consts_of(beta1, beta2, eps, weight_decay), clock, (hipStream_t)stream, who);
+}
+
+int rows_apply(const char* who, float* p0, float* m0, float* v0, const float* g0, float* p1,
+               float* m1, float* v1, const float* g1, int64_t dim, const int64_t* row_ids,
+               const uint32_t* count, int kind, int64_t max_n, int32_t* stamp, int32_t step,
+               const ncf_step_clock* clock, const float* step_table, double beta1, double beta2,
+               double eps, double weight_decay, void* stream) {
+  if (max_n <= 0) return NCF_OK;
+  NCF_CHECK_ARG(p0 && m0 && v0 && g0 && row_ids && stamp && step_table && (clock || step >= 1),
+                "%s: bad args", who);
+  NCF_CHECK_ARG(!p1 || g1, "%s: second table without gradient", who);
+  TablePtrs t{p0, m0, v0, p1, m1, v1, g0, g1};
+  NCF_DISPATCH_DIM(dim, apply_d, t, row_ids, count, kind, max_n, stamp, step, step_table,
+                   consts_of(beta1, beta2, eps, weight_decay), clock, (hipStream_t)stream, who);
 }
 
 template <int D>
@@ -589,30 +624,24 @@ int rolling_d(TablePtrs t, int64_t total, int64_t slice, int32_t every, int32_t*
 template <int D>
 int pairs_catchup_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, int32_t rel,
                     const ncf_step_clock* clock, const float* table, AdamScalars s,
-                    hipStream_t st, int lock = 0) {
-  if (a.dw)
-    hipLaunchKernelGGL((k_pairs_catchup<D, false, false, true>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
-  else if (a.sr)
-    hipLaunchKernelGGL((k_pairs_catchup<D, true, true>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
-  else if (a.bf)
-    hipLaunchKernelGGL((k_pairs_catchup<D, true>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
-  else
-    hipLaunchKernelGGL((k_pairs_catchup<D, false>), dim3(ncf_cdiv(max_n * Replay<D>::LPR, 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s, lock);
-  NCF_CHECK_LAUNCH("ncf_adam_pairs_catchup_clock");
+                    hipStream_t st, int lock, const char* who) {
+  const dim3 grid(ncf_cdiv(max_n * Replay<D>::LPR, 256), n);
+  for_any_rows(a.variant, [&](auto V) {
+    hipLaunchKernelGGL((k_pairs_catchup<D, V()>), grid, dim3(256), 0, st, a, count, max_n, rel,
+                       clock, table, s, lock);
+  });
+  NCF_CHECK_LAUNCH(who);
   return NCF_OK;
 }
 
 template <int D>
 int pairs_apply_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, int32_t rel,
                   const ncf_step_clock* clock, const float* table, AdamScalars s, hipStream_t st) {
-  if (a.dw)
-    hipLaunchKernelGGL((k_pairs_apply<D, false, false, true>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
-  else if (a.sr)
-    hipLaunchKernelGGL((k_pairs_apply<D, true, true>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
-  else if (a.bf)
-    hipLaunchKernelGGL((k_pairs_apply<D, true>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
-  else
-    hipLaunchKernelGGL((k_pairs_apply<D, false>), dim3(ncf_cdiv(max_n * (D / 4), 256), n), dim3(256), 0, st, a, count, max_n, rel, clock, table, s);
+  const dim3 grid(ncf_cdiv(max_n * (D / 4), 256), n);
+  for_any_rows(a.variant, [&](auto V) {
+    hipLaunchKernelGGL((k_pairs_apply<D, V()>), grid, dim3(256), 0, st, a, count, max_n, rel,
+                       clock, table, s);
+  });
   NCF_CHECK_LAUNCH("ncf_adam_pairs_apply_clock");
   return NCF_OK;
 }
@@ -623,10 +652,10 @@ int pairs_apply_gsum_d(PairArgs a, int n, const uint32_t* count, int64_t max_n, 
                        const float* got, const int32_t* pos0, const int32_t* pos1, int W,
                        hipStream_t st) {
   const dim3 grid(ncf_cdiv(max_n * (D / 4), 256), n);
-  if (a.bf)
-    hipLaunchKernelGGL((k_pairs_apply_gsum<D, true>), grid, dim3(256), 0, st, a, count, max_n, rel, clock, table, s, got, pos0, pos1, W);
-  else
-    hipLaunchKernelGGL((k_pairs_apply_gsum<D, false>), grid, dim3(256), 0, st, a, count, max_n, rel, clock, table, s, got, pos0, pos1, W);
+  for_rows<Rows::F32, Rows::BF16>(a.variant, [&](auto V) {   // (the entry admits no other)
+    hipLaunchKernelGGL((k_pairs_apply_gsum<D, RowTraits<V()>::BF>), grid, dim3(256), 0, st, a,
+                       count, max_n, rel, clock, table, s, got, pos0, pos1, W);
+  });
   NCF_CHECK_LAUNCH("ncf_adam_pairs_apply_gsum_clock");
   return NCF_OK;
 }
@@ -638,80 +667,44 @@ int64_t g_sweep_blocks_per_cu = 16;
 
 template <int D>
 int pairs_sweep_d(PairArgs a, int n, int32_t every, int32_t rel, const ncf_step_clock* clock,
-                  const float* table, AdamScalars s, hipStream_t st, int part = 0, int nparts = 1) {
+                  const float* table, AdamScalars s, hipStream_t st, int part, int nparts,
+                  const char* who) {
   int64_t slice = 0;
   for (int k = 0; k < n; ++k) slice = max(slice, (a.rows[k] + every - 1) / every);
   slice = (slice + nparts - 1) / nparts;
   const int gx = (int)min((int64_t)grid_for(slice * Replay<D>::LPR), 256 * g_sweep_blocks_per_cu);
-  if (a.dw)
-    hipLaunchKernelGGL((k_pairs_sweep<D, false, false, true>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
-  else if (a.sr)
-    hipLaunchKernelGGL((k_pairs_sweep<D, true, true>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
-  else if (a.bf)
-    hipLaunchKernelGGL((k_pairs_sweep<D, true>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
-  else
-    hipLaunchKernelGGL((k_pairs_sweep<D, false>), dim3(gx, n), dim3(256), 0, st, a, every, rel, clock, table, s, part, nparts);
-  NCF_CHECK_LAUNCH("ncf_adam_pairs_sweep_rolling");
+  for_any_rows(a.variant, [&](auto V) {
+    hipLaunchKernelGGL((k_pairs_sweep<D, V()>), dim3(gx, n), dim3(256), 0, st, a, every, rel,
+                       clock, table, s, part, nparts);
+  });
+  NCF_CHECK_LAUNCH(who);
   return NCF_OK;
 }
 
 template <int D>
 int sweep_d(TablePtrs t, int64_t row0, int64_t rows, int32_t* stamp, int32_t target,
-            const float* table, AdamScalars s, hipStream_t st, bool bf = false) {
-  if (bf)
-    hipLaunchKernelGGL((k_adam_sweep<D, true>), dim3(grid_for(rows * Replay<D>::LPR)), dim3(256), 0, st, t, row0, rows, stamp, target, table, s);
-  else
-    hipLaunchKernelGGL((k_adam_sweep<D, false>), dim3(grid_for(rows * Replay<D>::LPR)), dim3(256), 0, st, t, row0, rows, stamp, target, table, s);
-  NCF_CHECK_LAUNCH("ncf_adam_sweep");
+            const float* table, AdamScalars s, hipStream_t st, Rows rows_v, const char* who) {
+  for_rows<Rows::F32, Rows::BF16>(rows_v, [&](auto V) {
+    hipLaunchKernelGGL((k_adam_sweep<D, V()>), dim3(grid_for(rows * Replay<D>::LPR)), dim3(256),
+                       0, st, t, row0, rows, stamp, target, table, s);
+  });
+  NCF_CHECK_LAUNCH(who);
   return NCF_OK;
 }
 
-// the flat clock forms of both decay rules (dw: the decoupled table and element update)
-int flat_clock(const char* who, bool dw, float* param, const float* grad, float* exp_avg,
-               float* exp_avg_sq, int64_t n, const float* step_table, int32_t step_rel,
-               const ncf_step_clock* clock, double beta1, double beta2, double eps,
-               double weight_decay, void* stream) {
-  // (step_rel with the flag stripped: a value at or above the flag would be read as flagged)
-  NCF_CHECK_ARG(n >= 0 && step_rel < NCF_ADAM_DECOUPLED, "%s: bad args", who);
-  if (n == 0) return NCF_OK;
-  NCF_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step_table && clock,
+// What the two clock forms of the flat step share: the decay rule taken off step_rel (what is
+// left stays below the flag: a value at or above it would be read as flagged again), the checks
+// of the buffers, and the constants of that rule (decoupled: the decay is in the table and
+// weight_decay is not used).
+int flat_clock_begin(const char* who, const float* param, const float* grad, const float* exp_avg,
+                     const float* exp_avg_sq, int64_t n, const float* step_table,
+                     int32_t* step_rel, const ncf_step_clock* clock, double beta1, double beta2,
+                     double eps, double weight_decay, bool* dw, AdamScalars* s) {
+  *dw = take_dw(*step_rel);
+  NCF_CHECK_ARG(n >= 0 && *step_rel < NCF_ADAM_DECOUPLED, "%s: bad args", who);
+  NCF_CHECK_ARG(n == 0 || (param && grad && exp_avg && exp_avg_sq && step_table && clock),
                 "%s: null pointer", who);
-  const AdamScalars s = consts_of(beta1, beta2, eps, dw ? 0.0 : weight_decay);
-  if (dw)
-    hipLaunchKernelGGL(k_adam_flat_clock<true>, dim3(grid_for(n)), dim3(256), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, step_table,
-                       step_rel, clock, s);
-  else
-    hipLaunchKernelGGL(k_adam_flat_clock<false>, dim3(grid_for(n)), dim3(256), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, step_table,
-                       step_rel, clock, s);
-  NCF_CHECK_LAUNCH(who);
-  return NCF_OK;
-}
-
-int flat_close(const char* who, bool dw, float* param, const float* grad, float* exp_avg,
-               float* exp_avg_sq, int64_t n, const float* step_table, int32_t step_rel,
-               ncf_step_clock* clock, double beta1, double beta2, double eps,
-               double weight_decay, uint64_t base_seed, void* stream) {
-  NCF_CHECK_ARG(n >= 1 && param && grad && exp_avg && exp_avg_sq && step_table && clock &&
-                    step_rel < NCF_ADAM_DECOUPLED,
-                "%s: bad args", who);
-  NCF_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
-                "%s: buffers must be 16-B aligned", who);
-  // every block's arrival is one same-address atomic on the clock word: at most 64 blocks
-  // (was one per 256 elements, 328 at C2: the serialised atomics held the launch ~3 us)
-  int64_t nb = ((n >> 2) + 255) / 256;
-  nb = nb < 1 ? 1 : (nb > 64 ? 64 : nb);
-  const AdamScalars s = consts_of(beta1, beta2, eps, dw ? 0.0 : weight_decay);
-  if (dw)
-    hipLaunchKernelGGL(k_adam_flat_close<true>, dim3((unsigned)nb), dim3(256), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, step_table,
-                       step_rel, clock, base_seed, s);
-  else
-    hipLaunchKernelGGL(k_adam_flat_close<false>, dim3((unsigned)nb), dim3(256), 0,
-                       (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n, step_table,
-                       step_rel, clock, base_seed, s);
-  NCF_CHECK_LAUNCH(who);
+  *s = consts_of(beta1, beta2, eps, *dw ? 0.0 : weight_decay);
   return NCF_OK;
 }
 }  // namespace
@@ -737,11 +730,9 @@ extern "C" int ncf_adam_rows_catchup(float* p0, float* m0, float* v0, float* p1,
                                      int32_t* stamp, int32_t target, const float* step_table,
                                      double beta1, double beta2, double eps, double weight_decay,
                                      void* stream) {
-  if (max_n <= 0) return NCF_OK;
-  NCF_CHECK_ARG(p0 && m0 && v0 && row_ids && stamp && step_table, "ncf_adam_rows_catchup: null");
-  TablePtrs t{p0, m0, v0, p1, m1, v1, nullptr, nullptr};
-  NCF_DISPATCH_DIM(dim, catchup_d, t, row_ids, count, kind, max_n, stamp, target, step_table,
-                   consts_of(beta1, beta2, eps, weight_decay), nullptr, (hipStream_t)stream);
+  return rows_catchup("ncf_adam_rows_catchup", p0, m0, v0, p1, m1, v1, dim, row_ids, count, kind,
+                      max_n, stamp, target, nullptr, step_table, beta1, beta2, eps, weight_decay,
+                      stream);
 }
 
 extern "C" int ncf_adam_rows_apply(float* p0, float* m0, float* v0, const float* g0, float* p1,
@@ -750,13 +741,9 @@ extern "C" int ncf_adam_rows_apply(float* p0, float* m0, float* v0, const float*
                                    int64_t max_n, int32_t* stamp, int32_t step,
                                    const float* step_table, double beta1, double beta2,
                                    double eps, double weight_decay, void* stream) {
-  if (max_n <= 0) return NCF_OK;
-  NCF_CHECK_ARG(p0 && m0 && v0 && g0 && row_ids && stamp && step_table && step >= 1,
-                "ncf_adam_rows_apply: bad args");
-  NCF_CHECK_ARG(!p1 || g1, "ncf_adam_rows_apply: second table without gradient");
-  TablePtrs t{p0, m0, v0, p1, m1, v1, g0, g1};
-  NCF_DISPATCH_DIM(dim, apply_d, t, row_ids, count, kind, max_n, stamp, step, step_table,
-                   consts_of(beta1, beta2, eps, weight_decay), nullptr, (hipStream_t)stream);
+  return rows_apply("ncf_adam_rows_apply", p0, m0, v0, g0, p1, m1, v1, g1, dim, row_ids, count,
+                    kind, max_n, stamp, step, nullptr, step_table, beta1, beta2, eps,
+                    weight_decay, stream);
 }
 
 // rows [row0, row0 + rows) caught up to `target` (a rolling sweep passes one slice per step)
@@ -768,7 +755,8 @@ extern "C" int ncf_adam_sweep(float* p0, float* m0, float* v0, float* p1, float*
   NCF_CHECK_ARG(p0 && m0 && v0 && stamp && step_table && row0 >= 0, "ncf_adam_sweep: bad args");
   TablePtrs t{p0, m0, v0, p1, m1, v1, nullptr, nullptr};
   NCF_DISPATCH_DIM(dim, sweep_d, t, row0, rows, stamp, target, step_table,
-                   consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream);
+                   consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream, Rows::F32,
+                   "ncf_adam_sweep");
 }
 
 // bf16 parameter rows (fp32 moments): the same step / sweep, the parameter rounded to bf16
@@ -782,7 +770,7 @@ extern "C" int ncf_adam_table_bf16(uint16_t* param, float* exp_avg, float* exp_a
   NCF_CHECK_ARG(param && exp_avg && exp_avg_sq, "ncf_adam_table_bf16: null pointer");
   const AdamScalars s = make_scalars(lr, beta1, beta2, eps, weight_decay, step);
   NCF_DISPATCH_DIM(dim, table_d, reinterpret_cast<float*>(param), exp_avg, exp_avg_sq, rows, slot,
-                   grad_compact, s, (hipStream_t)stream, true);
+                   grad_compact, s, (hipStream_t)stream, Rows::BF16, "ncf_adam_table_bf16");
 }
 
 extern "C" int ncf_adam_sweep_bf16(uint16_t* p0, float* m0, float* v0, uint16_t* p1, float* m1,
@@ -795,7 +783,8 @@ extern "C" int ncf_adam_sweep_bf16(uint16_t* p0, float* m0, float* v0, uint16_t*
   TablePtrs t{reinterpret_cast<float*>(p0), m0, v0, reinterpret_cast<float*>(p1), m1, v1, nullptr,
               nullptr};
   NCF_DISPATCH_DIM(dim, sweep_d, t, row0, rows, stamp, target, step_table,
-                   consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream, true);
+                   consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream, Rows::BF16,
+                   "ncf_adam_sweep_bf16");
 }
 
 // ---- clock-driven forms (hipGraph-capturable training step)
@@ -813,12 +802,10 @@ extern "C" int ncf_adam_rows_catchup_clock(float* p0, float* m0, float* v0, floa
                                            const ncf_step_clock* clock, const float* step_table,
                                            double beta1, double beta2, double eps,
                                            double weight_decay, void* stream) {
-  if (max_n <= 0) return NCF_OK;
-  NCF_CHECK_ARG(p0 && m0 && v0 && row_ids && stamp && step_table && clock,
-                "ncf_adam_rows_catchup_clock: null");
-  TablePtrs t{p0, m0, v0, p1, m1, v1, nullptr, nullptr};
-  NCF_DISPATCH_DIM(dim, catchup_d, t, row_ids, count, kind, max_n, stamp, target_rel, step_table,
-                   consts_of(beta1, beta2, eps, weight_decay), clock, (hipStream_t)stream);
+  NCF_CHECK_ARG(clock || max_n <= 0, "ncf_adam_rows_catchup_clock: null");
+  return rows_catchup("ncf_adam_rows_catchup_clock", p0, m0, v0, p1, m1, v1, dim, row_ids, count,
+                      kind, max_n, stamp, target_rel, clock, step_table, beta1, beta2, eps,
+                      weight_decay, stream);
 }
 
 extern "C" int ncf_adam_rows_apply_clock(float* p0, float* m0, float* v0, const float* g0,
@@ -829,13 +816,10 @@ extern "C" int ncf_adam_rows_apply_clock(float* p0, float* m0, float* v0, const 
                                          const ncf_step_clock* clock, const float* step_table,
                                          double beta1, double beta2, double eps,
                                          double weight_decay, void* stream) {
-  if (max_n <= 0) return NCF_OK;
-  NCF_CHECK_ARG(p0 && m0 && v0 && g0 && row_ids && stamp && step_table && clock,
-                "ncf_adam_rows_apply_clock: bad args");
-  NCF_CHECK_ARG(!p1 || g1, "ncf_adam_rows_apply_clock: second table without gradient");
-  TablePtrs t{p0, m0, v0, p1, m1, v1, g0, g1};
-  NCF_DISPATCH_DIM(dim, apply_d, t, row_ids, count, kind, max_n, stamp, step_rel, step_table,
-                   consts_of(beta1, beta2, eps, weight_decay), clock, (hipStream_t)stream);
+  NCF_CHECK_ARG(clock || max_n <= 0, "ncf_adam_rows_apply_clock: bad args");
+  return rows_apply("ncf_adam_rows_apply_clock", p0, m0, v0, g0, p1, m1, v1, g1, dim, row_ids,
+                    count, kind, max_n, stamp, step_rel, clock, step_table, beta1, beta2, eps,
+                    weight_decay, stream);
 }
 
 extern "C" int ncf_adam_sweep_rolling(float* p0, float* m0, float* v0, float* p1, float* m1,
@@ -858,9 +842,17 @@ extern "C" int ncf_adam_flat_clock(float* param, const float* grad, float* exp_a
                                    float* exp_avg_sq, int64_t n, const float* step_table,
                                    int32_t step_rel, const ncf_step_clock* clock, double beta1,
                                    double beta2, double eps, double weight_decay, void* stream) {
-  return flat_clock("ncf_adam_flat_clock", step_rel >= 0 && (step_rel & NCF_ADAM_DECOUPLED), param, grad,
-                    exp_avg, exp_avg_sq, n, step_table, step_rel >= 0 ? step_rel & ~NCF_ADAM_DECOUPLED : step_rel, clock,
-                    beta1, beta2, eps, weight_decay, stream);
+  bool dw;
+  AdamScalars s;
+  const int rc = flat_clock_begin("ncf_adam_flat_clock", param, grad, exp_avg, exp_avg_sq, n,
+                                  step_table, &step_rel, clock, beta1, beta2, eps, weight_decay,
+                                  &dw, &s);
+  if (rc != NCF_OK || n == 0) return rc;
+  hipLaunchKernelGGL(dw ? k_adam_flat_clock<true> : k_adam_flat_clock<false>, dim3(grid_for(n)),
+                     dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
+                     step_table, step_rel, clock, s);
+  NCF_CHECK_LAUNCH("ncf_adam_flat_clock");
+  return NCF_OK;
 }
 
 extern "C" int ncf_adam_flat_clock_close(float* param, const float* grad, float* exp_avg,
@@ -868,23 +860,49 @@ extern "C" int ncf_adam_flat_clock_close(float* param, const float* grad, float*
                                          int32_t step_rel, ncf_step_clock* clock, double beta1,
                                          double beta2, double eps, double weight_decay,
                                          uint64_t base_seed, void* stream) {
-  return flat_close("ncf_adam_flat_clock_close", step_rel >= 0 && (step_rel & NCF_ADAM_DECOUPLED), param,
-                    grad, exp_avg, exp_avg_sq, n, step_table, step_rel >= 0 ? step_rel & ~NCF_ADAM_DECOUPLED : step_rel,
-                    clock, beta1, beta2, eps, weight_decay, base_seed, stream);
+  bool dw;
+  AdamScalars s;
+  const int rc = flat_clock_begin("ncf_adam_flat_clock_close", param, grad, exp_avg, exp_avg_sq,
+                                  n, step_table, &step_rel, clock, beta1, beta2, eps,
+                                  weight_decay, &dw, &s);
+  if (rc != NCF_OK) return rc;
+  NCF_CHECK_ARG(n >= 1, "ncf_adam_flat_clock_close: bad args");   // (the clock has to advance)
+  NCF_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0,
+                "ncf_adam_flat_clock_close: buffers must be 16-B aligned");
+  // every block's arrival is one same-address atomic on the clock word: at most 64 blocks
+  // (was one per 256 elements, 328 at C2: the serialised atomics held the launch ~3 us)
+  int64_t nb = ((n >> 2) + 255) / 256;
+  nb = nb < 1 ? 1 : (nb > 64 ? 64 : nb);
+  hipLaunchKernelGGL(dw ? k_adam_flat_close<true> : k_adam_flat_close<false>, dim3((unsigned)nb),
+                     dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
+                     step_table, step_rel, clock, base_seed, s);
+  NCF_CHECK_LAUNCH("ncf_adam_flat_clock_close");
+  return NCF_OK;
 }
 
+namespace {
+int pairs_catchup(const char* who, const ncf_table_pair* pairs, int npairs, int64_t dim,
+                  const uint32_t* count, int64_t max_n, int32_t target_rel, int32_t lock,
+                  const ncf_step_clock* clock, const float* step_table, double beta1,
+                  double beta2, double eps, double weight_decay, void* stream) {
+  PairArgs a;
+  const int rc = pair_args(who, pairs, npairs, &a);
+  if (rc != NCF_OK) return rc;
+  NCF_CHECK_ARG(count && clock && step_table && (lock == 0 || lock == 1), "%s: bad args", who);
+  if (max_n <= 0) return NCF_OK;
+  NCF_DISPATCH_DIM(dim, pairs_catchup_d, a, npairs, count, max_n, target_rel, clock, step_table,
+                   consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream, lock, who);
+}
+}  // namespace
+
+// (the catch-up without the row lock below)
 extern "C" int ncf_adam_pairs_catchup_clock(const ncf_table_pair* pairs, int npairs, int64_t dim,
                                             const uint32_t* count, int64_t max_n,
                                             int32_t target_rel, const ncf_step_clock* clock,
                                             const float* step_table, double beta1, double beta2,
                                             double eps, double weight_decay, void* stream) {
-  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table,
-                "ncf_adam_pairs_catchup_clock: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_catchup_clock: param_dtype");
-  if (max_n <= 0) return NCF_OK;
-  NCF_DISPATCH_DIM(dim, pairs_catchup_d, pair_args(pairs, npairs), npairs, count, max_n,
-                   target_rel, clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
-                   (hipStream_t)stream);
+  return pairs_catchup("ncf_adam_pairs_catchup_clock", pairs, npairs, dim, count, max_n,
+                       target_rel, 0, clock, step_table, beta1, beta2, eps, weight_decay, stream);
 }
 
 // lock = 1: every listed row is also marked in flight (stamp = target | NCF_STAMP_LOCK) until the
@@ -899,14 +917,9 @@ extern "C" int ncf_adam_pairs_catchup_lock_clock(const ncf_table_pair* pairs, in
                                                  const float* step_table, double beta1,
                                                  double beta2, double eps, double weight_decay,
                                                  void* stream) {
-  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table &&
-                    (lock == 0 || lock == 1),
-                "ncf_adam_pairs_catchup_lock_clock: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_catchup_lock_clock: param_dtype");
-  if (max_n <= 0) return NCF_OK;
-  NCF_DISPATCH_DIM(dim, pairs_catchup_d, pair_args(pairs, npairs), npairs, count, max_n,
-                   target_rel, clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
-                   (hipStream_t)stream, lock);
+  return pairs_catchup("ncf_adam_pairs_catchup_lock_clock", pairs, npairs, dim, count, max_n,
+                       target_rel, lock, clock, step_table, beta1, beta2, eps, weight_decay,
+                       stream);
 }
 
 template <int D>
@@ -914,18 +927,10 @@ int pairs_claim_d(PairArgs a, int npairs, const int64_t* ids0, const int64_t* id
                   int32_t rel, const ncf_step_clock* clock, const float* table, AdamScalars s,
                   hipStream_t st) {
   const dim3 grid((unsigned)ncf_cdiv(n * Replay<D>::LPR, 256), npairs);
-  if (a.dw)
-    hipLaunchKernelGGL((k_pairs_catchup_claim<D, false, false, true>), grid, dim3(256), 0, st, a, ids0,
-                       ids1, n, rel, clock, table, s);
-  else if (a.sr)
-    hipLaunchKernelGGL((k_pairs_catchup_claim<D, true, true>), grid, dim3(256), 0, st, a, ids0, ids1, n,
+  for_any_rows(a.variant, [&](auto V) {
+    hipLaunchKernelGGL((k_pairs_catchup_claim<D, V()>), grid, dim3(256), 0, st, a, ids0, ids1, n,
                        rel, clock, table, s);
-  else if (a.bf)
-    hipLaunchKernelGGL((k_pairs_catchup_claim<D, true>), grid, dim3(256), 0, st, a, ids0, ids1, n,
-                       rel, clock, table, s);
-  else
-    hipLaunchKernelGGL((k_pairs_catchup_claim<D, false>), grid, dim3(256), 0, st, a, ids0, ids1, n,
-                       rel, clock, table, s);
+  });
   NCF_CHECK_LAUNCH("ncf_adam_pairs_catchup_claim_clock");
   return NCF_OK;
 }
@@ -939,14 +944,14 @@ extern "C" int ncf_adam_pairs_catchup_claim_clock(const ncf_table_pair* pairs, i
                                                   const float* step_table, double beta1,
                                                   double beta2, double eps, double weight_decay,
                                                   void* stream) {
-  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && ids0 && (npairs < 2 || ids1) && clock &&
-                    step_table && n >= 0,
+  PairArgs a;
+  const int rc = pair_args("ncf_adam_pairs_catchup_claim_clock", pairs, npairs, &a);
+  if (rc != NCF_OK) return rc;
+  NCF_CHECK_ARG(ids0 && (npairs < 2 || ids1) && clock && step_table && n >= 0,
                 "ncf_adam_pairs_catchup_claim_clock: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_catchup_claim_clock: param_dtype");
   if (n == 0) return NCF_OK;
-  NCF_DISPATCH_DIM(dim, pairs_claim_d, pair_args(pairs, npairs), npairs, ids0, ids1, n,
-                   target_rel, clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
-                   (hipStream_t)stream);
+  NCF_DISPATCH_DIM(dim, pairs_claim_d, a, npairs, ids0, ids1, n, target_rel, clock, step_table,
+                   consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream);
 }
 
 extern "C" int ncf_adam_pairs_apply_clock(const ncf_table_pair* pairs, int npairs, int64_t dim,
@@ -954,15 +959,15 @@ extern "C" int ncf_adam_pairs_apply_clock(const ncf_table_pair* pairs, int npair
                                           const ncf_step_clock* clock, const float* step_table,
                                           double beta1, double beta2, double eps,
                                           double weight_decay, void* stream) {
-  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table,
-                "ncf_adam_pairs_apply_clock: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_apply_clock: param_dtype");
+  PairArgs a;
+  const int rc = pair_args("ncf_adam_pairs_apply_clock", pairs, npairs, &a);
+  if (rc != NCF_OK) return rc;
+  NCF_CHECK_ARG(count && clock && step_table, "ncf_adam_pairs_apply_clock: bad args");
   for (int k = 0; k < npairs; ++k)
     NCF_CHECK_ARG(pairs[k].g0 && (!pairs[k].p1 || pairs[k].g1), "ncf_adam_pairs_apply_clock: gradients");
   if (max_n <= 0) return NCF_OK;
-  NCF_DISPATCH_DIM(dim, pairs_apply_d, pair_args(pairs, npairs), npairs, count, max_n, step_rel,
-                   clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
-                   (hipStream_t)stream);
+  NCF_DISPATCH_DIM(dim, pairs_apply_d, a, npairs, count, max_n, step_rel, clock, step_table,
+                   consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream);
 }
 
 // ncf_shard_owner_gradsum + ncf_adam_pairs_apply_clock in one launch (the pairs' g0 / g1 unused)
@@ -974,32 +979,47 @@ extern "C" int ncf_adam_pairs_apply_gsum_clock(const ncf_table_pair* pairs, int 
                                                const float* step_table, double beta1,
                                                double beta2, double eps, double weight_decay,
                                                void* stream) {
-  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table && got &&
-                    pos0 && pos1 && world >= 1,
+  PairArgs a;
+  const int rc = pair_args("ncf_adam_pairs_apply_gsum_clock", pairs, npairs, &a);
+  if (rc != NCF_OK) return rc;
+  NCF_CHECK_ARG(count && clock && step_table && got && pos0 && pos1 && world >= 1,
                 "ncf_adam_pairs_apply_gsum_clock: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs) && pairs[0].param_dtype != NCF_DTYPE_BF16_SR &&
-                    !(pairs[0].param_dtype & NCF_ADAM_DECOUPLED),
+  NCF_CHECK_ARG(a.variant == Rows::F32 || a.variant == Rows::BF16,
                 "ncf_adam_pairs_apply_gsum_clock: param_dtype (no stochastic rounding and no "
                 "decoupled weight decay here)");
   for (int k = 0; k < npairs; ++k)
     NCF_CHECK_ARG(pairs[k].p1, "ncf_adam_pairs_apply_gsum_clock: both tables of a pair");
   if (max_n <= 0) return NCF_OK;
-  NCF_DISPATCH_DIM(dim, pairs_apply_gsum_d, pair_args(pairs, npairs), npairs, count, max_n,
-                   step_rel, clock, step_table, consts_of(beta1, beta2, eps, weight_decay), got,
-                   pos0, pos1, world, (hipStream_t)stream);
+  NCF_DISPATCH_DIM(dim, pairs_apply_gsum_d, a, npairs, count, max_n, step_rel, clock, step_table,
+                   consts_of(beta1, beta2, eps, weight_decay), got, pos0, pos1, world,
+                   (hipStream_t)stream);
 }
 
+namespace {
+int pairs_sweep(const char* who, const ncf_table_pair* pairs, int npairs, int64_t dim,
+                int32_t sweep_every, int32_t step_rel, int32_t part, int32_t nparts,
+                const ncf_step_clock* clock, const float* step_table, double beta1, double beta2,
+                double eps, double weight_decay, void* stream) {
+  PairArgs a;
+  const int rc = pair_args(who, pairs, npairs, &a);
+  if (rc != NCF_OK) return rc;
+  NCF_CHECK_ARG(clock && step_table && sweep_every >= 1 && nparts >= 1 && part >= 0 &&
+                    part < nparts,
+                "%s: bad args", who);
+  NCF_DISPATCH_DIM(dim, pairs_sweep_d, a, npairs, sweep_every, step_rel, clock, step_table,
+                   consts_of(beta1, beta2, eps, weight_decay), (hipStream_t)stream, part, nparts,
+                   who);
+}
+}  // namespace
+
+// the rolling sweep's slice of step clock->t + step_rel, both kinds: the whole slice
 extern "C" int ncf_adam_pairs_sweep_rolling(const ncf_table_pair* pairs, int npairs, int64_t dim,
                                             int32_t sweep_every, int32_t step_rel,
                                             const ncf_step_clock* clock, const float* step_table,
                                             double beta1, double beta2, double eps,
                                             double weight_decay, void* stream) {
-  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && clock && step_table && sweep_every >= 1,
-                "ncf_adam_pairs_sweep_rolling: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_sweep_rolling: param_dtype");
-  NCF_DISPATCH_DIM(dim, pairs_sweep_d, pair_args(pairs, npairs), npairs, sweep_every, step_rel,
-                   clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
-                   (hipStream_t)stream);
+  return pairs_sweep("ncf_adam_pairs_sweep_rolling", pairs, npairs, dim, sweep_every, step_rel, 0,
+                     1, clock, step_table, beta1, beta2, eps, weight_decay, stream);
 }
 
 // One of `nparts` consecutive row ranges of that slice (both kinds): the parts of a step can run
@@ -1011,13 +1031,9 @@ extern "C" int ncf_adam_pairs_sweep_rolling_part(const ncf_table_pair* pairs, in
                                                  const float* step_table, double beta1,
                                                  double beta2, double eps, double weight_decay,
                                                  void* stream) {
-  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && clock && step_table && sweep_every >= 1 &&
-                    nparts >= 1 && part >= 0 && part < nparts,
-                "ncf_adam_pairs_sweep_rolling_part: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_adam_pairs_sweep_rolling_part: param_dtype");
-  NCF_DISPATCH_DIM(dim, pairs_sweep_d, pair_args(pairs, npairs), npairs, sweep_every, step_rel,
-                   clock, step_table, consts_of(beta1, beta2, eps, weight_decay),
-                   (hipStream_t)stream, part, nparts);
+  return pairs_sweep("ncf_adam_pairs_sweep_rolling_part", pairs, npairs, dim, sweep_every,
+                     step_rel, part, nparts, clock, step_table, beta1, beta2, eps, weight_decay,
+                     stream);
 }
 
 extern "C" int64_t ncf_adam_sweep_set_blocks(int64_t per_cu) {

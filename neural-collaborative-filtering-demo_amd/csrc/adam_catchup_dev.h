@@ -4,6 +4,7 @@
 // and claim kernels of adam.hip and the fused tail launch of reduce.hip (k_reduce1_catchup) take
 // the same arithmetic in the same order, so every schedule gives the same bits.
 #pragma once
+#include <cstddef>
 #include "ncf_common.h"
 #include "adam_math.h"
 
@@ -34,26 +35,49 @@ struct Replay {
   static constexpr int EPL = D / LPR;           // columns per lane
 };
 
+// One owed zero-gradient step of one column, of one table or (PAIR) of both tables of a pair:
+// the variant's element update (step0) with the step's scalars ra / rb (/ dk, its decay, under
+// decoupled weight decay: one more float per step of the table, RowTraits<V>::TS), then the
+// variant's rounding of a bf16 parameter, which is stored (rounded) after every step it takes:
+// to nearest even, or stochastically with the step's bits (ncf_sr_*, ncf_common.h): key the
+// row's key of this step, ew the element's word (ncf_sr_elem).  Every loop that replays owed
+// steps calls this.
+template <Rows V, bool PAIR>
+__device__ __forceinline__ void owed_step(float& p0, float& m0, float& v0, float& p1, float& m1,
+                                          float& v1, float ra, float rb, float dk, uint32_t key,
+                                          uint32_t ew, const AdamScalars& s) {
+  using R = RowTraits<V>;
+  step0<R::DW>(p0, m0, v0, ra, rb, dk, s);
+  if (R::BF && !R::SR) p0 = ncf_round_bf16(p0);
+  if (PAIR) step0<R::DW>(p1, m1, v1, ra, rb, dk, s);
+  if (PAIR && R::BF && !R::SR) p1 = ncf_round_bf16(p1);
+  if (R::SR) {
+    const uint32_t h = ncf_sr_bits(key, ew);
+    p0 = ncf_sr_round0(p0, h);
+    if (PAIR) p1 = ncf_sr_round1(p1, h);
+  }
+}
+
 // The replay of zero-gradient steps from+1 .. to on EPL columns of one (pair of) table row(s).
 // With wave-uniform bounds (one row per wave) the per-step scalars are scalar loads; they are
 // fetched 8 steps (16 floats) at a time, one chunk AHEAD of the steps that use them, so the
 // scalar-load latency hides behind 8 steps of VALU work instead of stalling every step (the
 // step table is padded >= 4096 steps past any target, deferred.py _ensure).  Same adam1 calls in
 // the same order: results are bit-identical to the step-by-step loop.
-// SR (with BF): the parameter is rounded stochastically after every step, each step with its
-// own bits (ncf_sr_*, ncf_common.h): sr_base is the row's ncf_sr_base, wave-uniform like the
-// bounds, so a step's key is scalar work; e_lo the low word of the lane's first element.
-// DW: decoupled weight decay (adam_math.h): the table has StepTable<DW>::S floats per step and
-// the step's decay travels with ra / rb, a third scalar per owed step through the same scalar
-// loads and the same prefetch (NS scalars per step; the coupled form keeps its two).
-template <int EPL, bool PAIR, bool BF = false, bool SR = false, bool DW = false>
+// Stochastic rounding: sr_base is the row's ncf_sr_base, wave-uniform like the bounds, so a
+// step's key is scalar work; e_lo the low word of the lane's first element.
+// Decoupled weight decay: the step's decay travels with ra / rb, a third scalar per owed step
+// through the same scalar loads and the same prefetch (NS scalars per step; the coupled form
+// keeps its two).
+template <int EPL, bool PAIR, Rows V = Rows::F32>
 __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, float* p1,
                                                float* m1, float* v1, int32_t from, int32_t to,
                                                const float* __restrict__ table,
                                                const AdamScalars& s, uint32_t sr_base = 0,
                                                uint32_t e_lo = 0) {
+  constexpr bool SR = RowTraits<V>::SR, DW = RowTraits<V>::DW;
   constexpr int C = 8;                 // steps per chunk
-  constexpr int TS = StepTable<DW>::S; // floats per step of the table
+  constexpr int TS = RowTraits<V>::TS; // floats per step of the table
   constexpr int NS = DW ? 3 : 2;       // scalars a zero-gradient step reads: ra, rb (, decay)
   int32_t q = from + 1;
   uint32_t ew[EPL];                    // SR: the elements' words, the same at every step
@@ -80,17 +104,9 @@ __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, 
       const uint32_t key = SR ? ncf_sr_key(sr_base, q + k) : 0u;
       const float dk = DW ? sc[NS * k + NS - 1] : 1.f;
 #pragma unroll
-      for (int j = 0; j < EPL; ++j) {
-        step0<DW>(p0[j], m0[j], v0[j], sc[NS * k], sc[NS * k + 1], dk, s);
-        if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);   // bf16 tables: stored (rounded) every step
-        if (PAIR) step0<DW>(p1[j], m1[j], v1[j], sc[NS * k], sc[NS * k + 1], dk, s);
-        if (PAIR && BF && !SR) p1[j] = ncf_round_bf16(p1[j]);
-        if (SR) {
-          const uint32_t h = ncf_sr_bits(key, ew[j]);
-          p0[j] = ncf_sr_round0(p0[j], h);
-          if (PAIR) p1[j] = ncf_sr_round1(p1[j], h);
-        }
-      }
+      for (int j = 0; j < EPL; ++j)
+        owed_step<V, PAIR>(p0[j], m0[j], v0[j], p1[j], m1[j], v1[j], sc[NS * k], sc[NS * k + 1],
+                           dk, key, ew[j], s);
     }
 #pragma unroll
     for (int k = 0; k < NS * C; ++k) sc[k] = nx[k];
@@ -102,29 +118,21 @@ __device__ __forceinline__ void replay_uniform(float* p0, float* m0, float* v0, 
     const uint32_t key = SR ? ncf_sr_key(sr_base, q + k) : 0u;
     const float dk = DW ? sc[NS * k + NS - 1] : 1.f;
 #pragma unroll
-    for (int j = 0; j < EPL; ++j) {
-      step0<DW>(p0[j], m0[j], v0[j], sc[NS * k], sc[NS * k + 1], dk, s);
-      if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);
-      if (PAIR) step0<DW>(p1[j], m1[j], v1[j], sc[NS * k], sc[NS * k + 1], dk, s);
-      if (PAIR && BF && !SR) p1[j] = ncf_round_bf16(p1[j]);
-      if (SR) {
-        const uint32_t h = ncf_sr_bits(key, ew[j]);
-        p0[j] = ncf_sr_round0(p0[j], h);
-        if (PAIR) p1[j] = ncf_sr_round1(p1[j], h);
-      }
-    }
+    for (int j = 0; j < EPL; ++j)
+      owed_step<V, PAIR>(p0[j], m0[j], v0[j], p1[j], m1[j], v1[j], sc[NS * k], sc[NS * k + 1],
+                         dk, key, ew[j], s);
   }
 }
 
-// SR: stochastic rounding under `seed` for the tables of pair `kind` (ncf_sr_*)
-template <int D, bool BF = false, bool SR = false, bool DW = false>
+// Row `row` (columns sub, sub + LPR, ... of it) from step `from` to step `to`.  Stochastic
+// rounding runs under `seed` for the tables of pair `kind` (ncf_sr_*).
+template <int D, Rows V = Rows::F32>
 __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, int sub, int32_t from,
                                              int32_t to, const float* __restrict__ table,
                                              const AdamScalars& s, uint32_t seed = 0,
                                              int kind = 0) {
-  static_assert(BF || !SR, "stochastic rounding is a store of bf16 rows");
-  static_assert(!DW || !BF, "decoupled weight decay steps fp32 rows");
-  constexpr int TS = StepTable<DW>::S;
+  constexpr bool BF = RowTraits<V>::BF, SR = RowTraits<V>::SR, DW = RowTraits<V>::DW;
+  constexpr int TS = RowTraits<V>::TS;
   constexpr int EPL = Replay<D>::EPL, LPR = Replay<D>::LPR;
   if (Replay<D>::LPR == 64) {   // the whole wave holds this row: make the bounds scalar
     from = __builtin_amdgcn_readfirstlane(from);
@@ -149,13 +157,17 @@ __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, in
       p1[j] = ldp<BF>(t.p1, o + j * LPR); m1[j] = t.m1[o + j * LPR]; v1[j] = t.v1[o + j * LPR];
     }
     if (Replay<D>::LPR == 64) {
-      replay_uniform<EPL, true, BF, SR, DW>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
+      replay_uniform<EPL, true, V>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
     } else {
 #pragma unroll 2
       for (int32_t q = from + 1; q <= to; ++q) {
         const float ra = table[TS * q + 2], rb = table[TS * q + 3];
-      const float dk = DW ? table[TS * q + 4] : 1.f;
+        const float dk = DW ? table[TS * q + 4] : 1.f;
         const uint32_t key = SR ? ncf_sr_key(base, q) : 0u;
+        // Not owed_step<V, true>: this loop steps both tables before it rounds either, and with
+        // owed_step's order (round the first, then step the second) the compiler schedules the
+        // nearest-even bf16 form of two kernels differently at D < 64.  Same values either way;
+        // the loop keeps its order so that the machine code stays what was measured.
 #pragma unroll
         for (int j = 0; j < EPL; ++j) {
           step0<DW>(p0[j], m0[j], v0[j], ra, rb, dk, s);
@@ -174,7 +186,7 @@ __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, in
       stp<BF>(t.p1, o + j * LPR, p1[j]); t.m1[o + j * LPR] = m1[j]; t.v1[o + j * LPR] = v1[j];
     }
   } else if (Replay<D>::LPR == 64) {
-    replay_uniform<EPL, false, BF, SR, DW>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
+    replay_uniform<EPL, false, V>(p0, m0, v0, p1, m1, v1, from, to, table, s, base, e_lo);
   } else {
 #pragma unroll 2
     for (int32_t q = from + 1; q <= to; ++q) {
@@ -182,11 +194,9 @@ __device__ __forceinline__ void catch_up_row(const TablePtrs& t, int64_t row, in
       const float dk = DW ? table[TS * q + 4] : 1.f;
       const uint32_t key = SR ? ncf_sr_key(base, q) : 0u;
 #pragma unroll
-      for (int j = 0; j < EPL; ++j) {
-        step0<DW>(p0[j], m0[j], v0[j], ra, rb, dk, s);
-        if (BF && !SR) p0[j] = ncf_round_bf16(p0[j]);
-        if (SR) p0[j] = ncf_sr_round0(p0[j], ncf_sr_bits(key, ncf_sr_elem(e_lo + j * LPR)));
-      }
+      for (int j = 0; j < EPL; ++j)
+        owed_step<V, false>(p0[j], m0[j], v0[j], p1[j], m1[j], v1[j], ra, rb, dk, key,
+                            SR ? ncf_sr_elem(e_lo + j * LPR) : 0u, s);
     }
   }
 #pragma unroll
@@ -201,44 +211,36 @@ struct PairArgs {
   const int64_t* ids[2];
   int32_t* stamp[2];
   int64_t rows[2];
-  int bf;            // parameter rows are bf16 (host-side dispatch only)
-  int sr;            // ... and rounded stochastically (NCF_DTYPE_BF16_SR; host-side dispatch)
+  Rows variant;      // which instantiation the host launches (rows_of); no kernel reads it
+  int32_t reserved0;
   uint32_t seed;     // round_seed of the stochastic rounding (ncf_sr_base)
-  int dw;            // decoupled weight decay (NCF_ADAM_DECOUPLED; host-side dispatch)
+  int32_t reserved1;
 };
-static_assert(sizeof(PairArgs) == 192, "PairArgs: dw sits in the tail padding (kernel arguments)");
+static_assert(sizeof(PairArgs) == 192 && offsetof(PairArgs, seed) == 184,
+              "PairArgs: kernel arguments, the offsets the kernels load from stay put");
 
-// whether the n pairs name one parameter dtype this build knows (NCF_DTYPE_*)
-inline bool pair_dtypes_ok(const ncf_table_pair* p, int n) {
-  for (int k = 0; k < n && k < 2; ++k)
-    if (p[k].param_dtype != p[0].param_dtype || p[k].round_seed != p[0].round_seed) return false;
-  // (decoupled weight decay: fp32 rows only)
-  if (p[0].param_dtype & NCF_ADAM_DECOUPLED)
-    return p[0].param_dtype == (NCF_DTYPE_F32 | NCF_ADAM_DECOUPLED);
-  return p[0].param_dtype == NCF_DTYPE_F32 || p[0].param_dtype == NCF_DTYPE_BF16 ||
-         p[0].param_dtype == NCF_DTYPE_BF16_SR;
-}
-
-inline PairArgs pair_args(const ncf_table_pair* p, int n) {
+// The launch arguments of the n (1 or 2) pairs an entry point was given, or NCF_ERR_ARG: what
+// every pairs entry checks of its tables (the variant: rows_of, adam_math.h).
+inline int pair_args(const char* who, const ncf_table_pair* p, int n, PairArgs* out) {
+  NCF_CHECK_ARG(p && n >= 1 && n <= 2, "%s: bad args", who);
   PairArgs a;
   memset(&a, 0, sizeof(a));
-  for (int k = 0; k < n && k < 2; ++k) {
+  const int rc = rows_of(who, p, n, &a.variant);
+  if (rc != NCF_OK) return rc;
+  for (int k = 0; k < n; ++k) {
     a.t[k] = TablePtrs{p[k].p0, p[k].m0, p[k].v0, p[k].p1, p[k].m1, p[k].v1, p[k].g0, p[k].g1};
     a.ids[k] = p[k].row_ids;
     a.stamp[k] = p[k].stamp;
     a.rows[k] = p[k].rows;
   }
-  a.dw = (p[0].param_dtype & NCF_ADAM_DECOUPLED) != 0;
-  const int32_t dt = p[0].param_dtype & ~NCF_ADAM_DECOUPLED;
-  a.sr = dt == NCF_DTYPE_BF16_SR;
-  a.bf = a.sr || dt == NCF_DTYPE_BF16;
   a.seed = (uint32_t)p[0].round_seed;
-  return a;
+  *out = a;
+  return NCF_OK;
 }
 
 // Block bx (of ncf_cdiv(max_n * Replay<D>::LPR, 256), 256 threads) of the catch-up of kind k's
 // listed rows ids[k][0 .. count[k]) to clock->t + target_rel.
-template <int D, bool BF, bool SR = false, bool DW = false>
+template <int D, Rows V>
 __device__ __forceinline__ void pairs_catchup_body(const PairArgs& a, int k, uint32_t bx,
                                                    const uint32_t* __restrict__ count,
                                                    int64_t max_n, int32_t target_rel,
@@ -254,7 +256,7 @@ __device__ __forceinline__ void pairs_catchup_body(const PairArgs& a, int k, uin
   const int64_t row = a.ids[k][c];
   int32_t* stamp = a.stamp[k];
   const int32_t from = stamp[row];
-  catch_up_row<D, BF, SR, DW>(a.t[k], row, sub, from, target, table, s, a.seed, k);
+  catch_up_row<D, V>(a.t[k], row, sub, from, target, table, s, a.seed, k);
   // lock: every listed row is marked in flight (current through target, its gradient step still
   // to come: the step's apply writes the plain stamp back); replays of other rows skip it.  A
   // listed row that is locked already, or ahead of the target, keeps its stamp: it was not

@@ -3,6 +3,7 @@
 // same bits.  torch.optim.Adam semantics (src/model/trainer.py:71-75, :285); see adam.hip.
 #pragma once
 #include <cmath>
+#include <type_traits>
 #include "ncf_common.h"
 
 namespace ncf_adam {
@@ -114,10 +115,55 @@ __device__ __forceinline__ void step4(float4& p, float4& m, float4& v, float4 g,
 
 // floats per step of the per-step scalar table a kernel reads: 4 (ncf_adam_step_scalars) or
 // NCF_ADAMW_TABLE_STRIDE with the step's decay at index 4 (include/ncf_hip.h)
-template <bool DW>
-struct StepTable {
-  static constexpr int S = DW ? NCF_ADAMW_TABLE_STRIDE : 4;
+constexpr int step_stride(bool dw) { return dw ? NCF_ADAMW_TABLE_STRIDE : 4; }
+
+// ---- the row variant of a table kernel -----------------------------------------------------
+// What the rows of a table are and how they step: fp32 rows, bf16 rows rounded to nearest even
+// or stochastically after every step they take, fp32 rows under decoupled weight decay.  These
+// four exist (ncf_table_pair's param_dtype, include/ncf_hip.h); a table kernel is instantiated
+// per variant, <int D, Rows V>, and reads the variant's properties from RowTraits<V>.
+enum class Rows : int { F32, BF16, BF16_SR, F32_DW };
+
+template <Rows V>
+struct RowTraits {
+  static constexpr bool BF = V == Rows::BF16 || V == Rows::BF16_SR;   // the parameter is bf16
+  static constexpr bool SR = V == Rows::BF16_SR;                       // ... rounded stochastically
+  static constexpr bool DW = V == Rows::F32_DW;                        // decoupled weight decay
+  static constexpr int TS = step_stride(DW);                           // step table stride
 };
+
+// Host dispatch: f(tag) with the compile-time tag (tag() == v) of the one variant among Vs that
+// v names; false, and no call, if it names none of them.
+//   for_rows<Rows::F32, Rows::BF16>(v, [&](auto V) { hipLaunchKernelGGL((k<D, V()>), ...); });
+template <Rows V>
+using RowsTag = std::integral_constant<Rows, V>;
+
+template <Rows... Vs, class F>
+inline bool for_rows(Rows v, F&& f) {
+  return ((v == Vs && (f(RowsTag<Vs>{}), true)) || ...);
+}
+
+template <class F>
+inline void for_any_rows(Rows v, F&& f) {
+  for_rows<Rows::F32, Rows::BF16, Rows::BF16_SR, Rows::F32_DW>(v, f);
+}
+
+// The variant n table pairs name, or NCF_ERR_ARG (the error names `who`, the entry point called):
+// a param_dtype this build knows (NCF_DTYPE_*; NCF_ADAM_DECOUPLED with fp32 rows only), the same
+// in every pair, as round_seed is.
+inline int rows_of(const char* who, const ncf_table_pair* p, int n, Rows* out) {
+  for (int k = 1; k < n; ++k)
+    NCF_CHECK_ARG(p[k].param_dtype == p[0].param_dtype && p[k].round_seed == p[0].round_seed,
+                  "%s: param_dtype (the pairs differ)", who);
+  switch (p[0].param_dtype) {
+    case NCF_DTYPE_F32: *out = Rows::F32; return NCF_OK;
+    case NCF_DTYPE_BF16: *out = Rows::BF16; return NCF_OK;
+    case NCF_DTYPE_BF16_SR: *out = Rows::BF16_SR; return NCF_OK;
+    case NCF_DTYPE_F32 | NCF_ADAM_DECOUPLED: *out = Rows::F32_DW; return NCF_OK;
+  }
+  ncf_set_error("%s: param_dtype %d", who, (int)p[0].param_dtype);
+  return NCF_ERR_ARG;
+}
 
 inline float decay_of(double lr, double wd) { return (float)(1.0 - lr * wd); }
 

@@ -475,16 +475,13 @@ extern "C" int ncf_embedding_bwd_reduce_apply_clock(
     const float* step_table, double beta1, double beta2, double eps_adam, double weight_decay,
     void* stream) {
   NCF_CHECK_ARG(pairs && clock && step_table, "ncf_embedding_bwd_reduce_apply_clock: bad args");
-  NCF_CHECK_ARG(pairs[0].param_dtype == NCF_DTYPE_F32 || pairs[0].param_dtype == NCF_DTYPE_BF16 ||
-                    pairs[0].param_dtype == NCF_DTYPE_BF16_SR ||
-                    pairs[0].param_dtype == (NCF_DTYPE_F32 | NCF_ADAM_DECOUPLED),
-                "ncf_embedding_bwd_reduce_apply_clock: param_dtype");
+  ncf_adam::Rows rows;
+  const int rv = ncf_adam::rows_of("ncf_embedding_bwd_reduce_apply_clock", pairs, 2, &rows);
+  if (rv != NCF_OK) return rv;
   ApplyArgs ap{};
   for (int k = 0; k < 2; ++k) {
     NCF_CHECK_ARG(pairs[k].p0 && pairs[k].m0 && pairs[k].v0 && pairs[k].p1 && pairs[k].m1 &&
-                      pairs[k].v1 && pairs[k].stamp &&
-                      pairs[k].param_dtype == pairs[0].param_dtype &&
-                      pairs[k].round_seed == pairs[0].round_seed,
+                      pairs[k].v1 && pairs[k].stamp,
                   "ncf_embedding_bwd_reduce_apply_clock: incomplete table pair");
     ap.p[k][0] = pairs[k].p0; ap.m[k][0] = pairs[k].m0; ap.v[k][0] = pairs[k].v0;
     ap.p[k][1] = pairs[k].p1; ap.m[k][1] = pairs[k].m1; ap.v[k][1] = pairs[k].v1;
@@ -495,8 +492,8 @@ extern "C" int ncf_embedding_bwd_reduce_apply_clock(
   ap.s = ncf_adam::consts_of(beta1, beta2, eps_adam, weight_decay);
   ap.step_rel = step_rel;
   ap.on = 1;
-  const bool decoupled = (pairs[0].param_dtype & NCF_ADAM_DECOUPLED) != 0;
-  if (pairs[0].param_dtype == NCF_DTYPE_BF16_SR || decoupled) {
+  const bool decoupled = rows == ncf_adam::Rows::F32_DW;
+  if (rows == ncf_adam::Rows::BF16_SR || decoupled) {
     // Stochastic rounding: the reduce as ncf_embedding_bwd_reduce_bf16 runs it, then the apply
     // as its own launch (ncf_adam_pairs_apply_clock over this call's unique rows and compact
     // gradients; totals[k] of the workspace is num_unique[k]).  Not inside the reduce: a third
@@ -519,7 +516,7 @@ extern "C" int ncf_embedding_bwd_reduce_apply_clock(
                                       clock, step_table, beta1, beta2, eps_adam, weight_decay,
                                       stream);
   }
-  const bool bf = pairs[0].param_dtype == NCF_DTYPE_BF16;
+  const bool bf = rows == ncf_adam::Rows::BF16;
   return embedding_bwd_reduce(bf, n, dim, num_users, num_items, dy_mf_user, dy_mlp_user,
                               dy_mf_item, dy_mlp_item, pairs[0].p0, pairs[0].p1, pairs[1].p0,
                               pairs[1].p1, mf_gamma, mlp_gamma, eps, grad_mf_user, grad_mlp_user,

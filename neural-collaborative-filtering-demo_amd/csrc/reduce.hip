@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void k_reduce_batch1(const BatchArgs a, float*
 // loads (28 B of scratch per lane) 28 us, with 4 loads (50 registers at D <= 128, no scratch)
 // 27 us; DESIGN §15.
 constexpr int kTailLoads = 4;
-template <int D, bool BF, bool SR = false, bool DW = false>
+template <int D, Rows V>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_reduce1_catchup(const BatchArgs a,
                                                          float* __restrict__ scratch, uint32_t nred,
                                                          const PairArgs pa,
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
   }
   if (catchup)
-    pairs_catchup_body<D, BF, SR, DW>(pa, k, b, count, max_n, target_rel, clock, table, s, 0);
+    pairs_catchup_body<D, V>(pa, k, b, count, max_n, target_rel, clock, table, s, 0);
   else
     reduce1_body<kTailLoads>(a, scratch, b, red);
 }
@@ -216,21 +216,22 @@ struct Tail {
 // resource report), so that width takes the reduce and the catch-up as two launches: same bits.
 constexpr int kDwFusedMaxDim = 128;
 
+// whether rows of width dim and variant v have an instantiation of the fused kernel: asked by
+// its launch (fused_d) and by ncf_reduce_batch_catchup, which makes the two launches otherwise
+constexpr bool tail_fused(int64_t dim, Rows v) {
+  return v != Rows::F32_DW || dim <= kDwFusedMaxDim;
+}
+
 template <int D>
 int fused_d(const BatchArgs& a1, float* scratch, uint32_t b1, const Tail& t, hipStream_t st) {
   const uint32_t ncx = (uint32_t)ncf_cdiv(t.max_n * Replay<D>::LPR, 256);
   const dim3 grid(b1 + (uint32_t)t.npairs * ncx);
-  if (t.pa.dw) {   // decoupled weight decay (NCF_ADAM_DECOUPLED): the decoupled step table
-    // (D = 256 is not fused, kDwFusedMaxDim: ncf_reduce_batch_catchup makes the two launches)
-    if constexpr (D <= kDwFusedMaxDim)
-      hipLaunchKernelGGL((k_reduce1_catchup<D, false, false, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
-    // (wider rows never get here: no instantiation of the fused kernel for them)
-  } else if (t.pa.sr)
-    hipLaunchKernelGGL((k_reduce1_catchup<D, true, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
-  else if (t.pa.bf)
-    hipLaunchKernelGGL((k_reduce1_catchup<D, true>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
-  else
-    hipLaunchKernelGGL((k_reduce1_catchup<D, false>), grid, dim3(256), 0, st, a1, scratch, b1, t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx, TAIL_ORDER);
+  for_any_rows(t.pa.variant, [&](auto V) {
+    if constexpr (tail_fused(D, V()))   // (the others never get here)
+      hipLaunchKernelGGL((k_reduce1_catchup<D, V()>), grid, dim3(256), 0, st, a1, scratch, b1,
+                         t.pa, t.count, t.max_n, t.target_rel, t.clock, t.table, t.s, ncx,
+                         TAIL_ORDER);
+  });
   NCF_CHECK_LAUNCH("ncf_reduce_batch_catchup(stage 1 + catch-up)");
   return NCF_OK;
 }
@@ -326,13 +327,15 @@ extern "C" int ncf_reduce_batch_catchup(const ncf_reduce_list* list, float* scra
                                         double weight_decay, void* stream) {
   NCF_CHECK_ARG(list && list->count >= 0 && list->count <= NCF_REDUCE_LIST_MAX,
                 "ncf_reduce_batch_catchup: bad list");
-  NCF_CHECK_ARG(pairs && npairs >= 1 && npairs <= 2 && count && clock && step_table,
-                "ncf_reduce_batch_catchup: bad args");
-  NCF_CHECK_ARG(pair_dtypes_ok(pairs, npairs), "ncf_reduce_batch_catchup: param_dtype");
+  Tail tail{{}, npairs, dim, count, max_n, target_rel, clock, step_table,
+            consts_of(beta1, beta2, eps, weight_decay)};
+  const int rc = pair_args("ncf_reduce_batch_catchup", pairs, npairs, &tail.pa);
+  if (rc != NCF_OK) return rc;
+  NCF_CHECK_ARG(count && clock && step_table, "ncf_reduce_batch_catchup: bad args");
   if (max_n <= 0)
     return run_list("ncf_reduce_batch_catchup", list, scratch, scratch_floats, nullptr,
                     (hipStream_t)stream);
-  if ((pairs[0].param_dtype & NCF_ADAM_DECOUPLED) && dim > kDwFusedMaxDim) {
+  if (!tail_fused(dim, tail.pa.variant)) {
     const int rc = run_list("ncf_reduce_batch_catchup", list, scratch, scratch_floats, nullptr,
                             (hipStream_t)stream);
     if (rc != NCF_OK) return rc;
@@ -344,8 +347,6 @@ extern "C" int ncf_reduce_batch_catchup(const ncf_reduce_list* list, float* scra
     return ncf_adam_pairs_catchup_lock_clock(pairs, npairs, dim, count, max_n, target_rel, 0,
                                              clock, step_table, beta1, beta2, eps, weight_decay,
                                              stream);
-  const Tail tail{pair_args(pairs, npairs), npairs, dim, count, max_n, target_rel, clock,
-                  step_table, consts_of(beta1, beta2, eps, weight_decay)};
   return run_list("ncf_reduce_batch_catchup", list, scratch, scratch_floats, &tail,
                   (hipStream_t)stream);
 }

@@ -84,7 +84,8 @@ def main():
     asm = open(src).read()
     res = {}
     for sym, body in kernels(asm).items():
-        m = re.search(r"k_pairs_(sweep|catchup_claim|catchup)ILi(64|128)ELb0E", sym)
+        # <D, Rows::F32>: the variant is mangled as the enumerator's value (L<type>0E)
+        m = re.search(r"k_pairs_(sweep|catchup_claim|catchup)ILi(64|128)ELN\w*4RowsE0EE", sym)
         if not m:
             continue
         best = None

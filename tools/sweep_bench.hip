@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void k_sweep_v2(const PairArgs a, int32_t ever
     const int sub = (int)(e % L);
     int32_t* stamp = a.stamp[k];
     const int32_t from = stamp[row];
-    catch_up_row<D, false>(a.t[k], row, sub, from, target, table, s);
+    catch_up_row<D>(a.t[k], row, sub, from, target, table, s);
     if (sub == 0 && from < target) stamp[row] = target;
   }
 }
