@@ -174,7 +174,30 @@ int ncf_bag_pool_fwd(const int64_t* ids, int64_t n_ids, const int64_t* offsets, 
  * sums are added in chunk order, so the result is a pure function of the input.  Ids out of
  * range and positions no bag holds contribute nothing.  grad_table may be NULL when only
  * grad_weights is wanted (no sort then); table may be NULL when grad_weights is.  workspace:
- * ncf_bag_pool_bwd_workspace(n_ids, bags, dim) bytes.  n_ids < 2^30, rows <= 2^32.          */
+ * ncf_bag_pool_bwd_workspace(n_ids, bags, dim) bytes.  n_ids < 2^30, rows <= 2^32.
+ *
+ * NCF_BAG_COMPACT, a flag ORed into `mode` of ncf_bag_pool_bwd (mode & ~NCF_BAG_COMPACT is still 0
+ * or 1; any other bit, and the flag on ncf_bag_pool_fwd, is NCF_ERR_ARG): grad_table is a compact
+ * buffer with room for min(n_ids, rows) rows of dim floats, and row c receives the gradient of
+ * the c-th unique id: bit for bit what the dense call stores at row ids_out[c] (the same chunks,
+ * the same order in a chunk, the same order of the chunks).  Nothing is zero-filled and rows
+ * >= U are not written: the call touches O(n_ids) memory, whatever `rows` is.  U and the unique
+ * ids come back in the head of the workspace (the same workspace size serves both forms):
+ *   uint32 U             at byte NCF_BAG_WS_COUNT_OFFSET
+ *   int64  ids_out[U]    at byte NCF_BAG_WS_IDS_OFFSET   (room for n_ids + 2; scratch follows)
+ * ids_out is ascending, without repeats, every entry in [0, rows).  What is listed:
+ *   - an id all of whose positions lie outside every bag is listed, with a row of exact +0.0
+ *     (the ids are sorted whatever the offsets say; the dense call stores the same zeros);
+ *   - an id outside [0, rows) is listed nowhere and nothing is written for it.  Its position is
+ *     counted with row 0's (the sort's clamp), where it contributes nothing: so when any id is
+ *     out of range, row 0 is listed, with an exact zero row unless in-range positions name it.
+ * n_ids == 0 or rows == 0: U = 0 and nothing else is written.  grad_table and workspace must
+ * not be NULL with the flag; grad_weights is as without it.  Without the flag every output is
+ * as before; the workspace is scratch either way, and the call that sorts (grad_table not NULL,
+ * n_ids > 0, rows > 0) leaves U and ids_out at its head in both forms.                      */
+#define NCF_BAG_COMPACT 0x100
+#define NCF_BAG_WS_COUNT_OFFSET 0
+#define NCF_BAG_WS_IDS_OFFSET 256
 int64_t ncf_bag_pool_bwd_workspace(int64_t n_ids, int64_t bags, int64_t dim);
 int ncf_bag_pool_bwd(const int64_t* ids, int64_t n_ids, const int64_t* offsets, int64_t bags,
                      const float* weights, const float* table, const float* grad_out,

@@ -17,5 +17,6 @@ from .scoring import SeenItems, score_rank  # noqa: F401
 from .metrics import ranking_report  # noqa: F401
 from .neighbors import ProductSearch  # noqa: F401
 from .clip import clip_grad_norm_, grad_norm  # noqa: F401
+from .optim import SparseAdam  # noqa: F401
 
 __version__ = "1.0.0"

@@ -61,6 +61,10 @@ DTYPE_F32, DTYPE_BF16 = DEFINES["NCF_DTYPE_F32"], DEFINES["NCF_DTYPE_BF16"]
 DTYPE_BF16_SR = DEFINES["NCF_DTYPE_BF16_SR"]     # bf16 rows, rounded stochastically
 ADAM_DECOUPLED = DEFINES["NCF_ADAM_DECOUPLED"]   # flag in param_dtype: AdamW's decay rule
 ADAMW_TABLE_STRIDE = DEFINES["NCF_ADAMW_TABLE_STRIDE"]   # floats per step, decoupled table
+BAG_COMPACT = DEFINES["NCF_BAG_COMPACT"]         # flag in ncf_bag_pool_bwd's mode: compact rows
+# the compact call's output block in its workspace: uint32 U, int64 unique ids (byte offsets)
+BAG_WS_COUNT_OFFSET = DEFINES["NCF_BAG_WS_COUNT_OFFSET"]
+BAG_WS_IDS_OFFSET = DEFINES["NCF_BAG_WS_IDS_OFFSET"]
 
 _MIRRORS = {}   # header struct name -> its ctypes.Structure below
 

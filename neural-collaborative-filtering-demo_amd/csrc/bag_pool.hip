@@ -18,6 +18,12 @@
 // to its gradient row; of a longer segment the first piece goes to the row, the others to a
 // partial row each (the workspace's xp0 rows), and k_bag_combine adds the partial rows to the
 // gradient row in piece order.  Every step is a pure function of the input: bitwise reproducible.
+//
+// Compact destination (NCF_BAG_COMPACT): the same pieces and the same combine with the gradient
+// row of segment c at row c of a [U, D] buffer instead of row uniq[c] of the dense one
+// (k_bag_pieces / k_bag_combine<D, COMPACT>: a compile-time choice of the destination index, so
+// the dense instantiations are the kernels they were).  Nothing is zero-filled; U and the unique
+// ids are read from the head of the workspace (include/ncf_hip.h).
 #include "segments.h"
 
 // Each multiply and add is its own IEEE operation (no fma contraction), as in gather_ln.hip: the
@@ -131,8 +137,15 @@ __global__ __launch_bounds__(256) void k_bag_pos(const int64_t* __restrict__ ids
   pos_coef[p] = coef;
 }
 
+// row of segment c in the gradient buffer: uniq[c] (dense [rows, D]) or c (compact [U, D])
+template <bool COMPACT>
+__device__ __forceinline__ int64_t dest_row(const int64_t* __restrict__ uniq, uint32_t c) {
+  if (COMPACT) return (int64_t)c;
+  return uniq[c];
+}
+
 // one lane group per piece (<= PIECE sorted positions of one id), summed in sorted-position order
-template <int D>
+template <int D, bool COMPACT>
 __global__ __launch_bounds__(256) void k_bag_pieces(
     const uint32_t* __restrict__ sv, const uint32_t* __restrict__ pstart,
     const uint32_t* __restrict__ pseg, const int64_t* __restrict__ uniq,
@@ -163,13 +176,13 @@ __global__ __launch_bounds__(256) void k_bag_pieces(
       for (int j = 0; j < kPieceInFlight; ++j)
         if (i + j < i1) acc = f4_add(acc, g[j]);
     }
-    if (ps & FIRST_PIECE) st4(grad_table + uniq[c] * D + c4, acc);
+    if (ps & FIRST_PIECE) st4(grad_table + dest_row<COMPACT>(uniq, c) * D + c4, acc);
     else st4(partial + (p - c - 1) * D + c4, acc);   // non-first pieces before p: p - (c + 1)
   }
 }
 
 // segments of more than one piece: gradient row (its first piece) + the partial rows, in order
-template <int D>
+template <int D, bool COMPACT>
 __global__ __launch_bounds__(256) void k_bag_combine(const uint32_t* __restrict__ fpiece,
                                                      const int64_t* __restrict__ uniq,
                                                      const uint32_t* __restrict__ totals,
@@ -182,7 +195,7 @@ __global__ __launch_bounds__(256) void k_bag_combine(const uint32_t* __restrict_
        c += (int64_t)gridDim.x * G) {
     const int64_t p0 = fpiece[c], p1 = fpiece[c + 1];
     if (p1 - p0 <= 1) continue;
-    float* row = grad_table + uniq[c] * D + c4;
+    float* row = grad_table + dest_row<COMPACT>(uniq, (uint32_t)c) * D + c4;
     float4 acc = ld4(row);
     const float* part = partial + (p0 - c) * D + c4;   // partial row of piece p0 + 1
     const int64_t m = p1 - p0 - 1;
@@ -241,47 +254,64 @@ int launch_bag_fwd(const int64_t* ids, int64_t n_ids, const int64_t* offsets, in
   return NCF_OK;
 }
 
-// workspace: the dedup's (segments.h) | uniq ids int64[n + 2] | pos_bag int32[n] | pos_coef f32[n]
+// workspace: the output block (include/ncf_hip.h: U uint32[2] at NCF_BAG_WS_COUNT_OFFSET, uniq ids
+// int64[n + 2] at NCF_BAG_WS_IDS_OFFSET) | the dedup's (segments.h) | pos_bag int32[n] | pos_coef
+// f32[n]; one layout and one size for the dense and the compact call
 struct BagWS {
+  uint32_t* count;
+  int64_t* uniq;
   void* dedup;
   int64_t dedup_bytes;
-  int64_t* uniq;
   int32_t* pos_bag;
   float* pos_coef;
 };
+static_assert(NCF_BAG_WS_COUNT_OFFSET == 0 && NCF_BAG_WS_IDS_OFFSET == 256, "workspace head");
 int64_t bag_ws_bytes(int64_t n, int64_t D) {
-  return ws_bytes(n, D) + round256(8 * (n + 2)) + 2 * round256(4 * (n + 2));
+  return NCF_BAG_WS_IDS_OFFSET + round256(8 * (n + 2)) + round256(ws_bytes(n, D)) +
+         2 * round256(4 * (n + 2));
 }
 BagWS bag_carve(void* base, int64_t n, int64_t D) {
   BagWS w;
   char* p = (char*)base;
+  w.count = (uint32_t*)(p + NCF_BAG_WS_COUNT_OFFSET);
+  p += NCF_BAG_WS_IDS_OFFSET;
+  w.uniq = (int64_t*)p;
+  p += round256(8 * (n + 2));
   w.dedup = p;
   w.dedup_bytes = ws_bytes(n, D);
   p += round256(w.dedup_bytes);
-  w.uniq = (int64_t*)p;
-  p += round256(8 * (n + 2));
   w.pos_bag = (int32_t*)p;
   p += round256(4 * (n + 2));
   w.pos_coef = (float*)p;
   return w;
 }
 
+template <int D, bool COMPACT>
+int launch_bag_table_grad(const WS& w, const uint32_t* sv, const BagWS& b, int64_t n_ids,
+                          const float* grad_out, float* grad_table, hipStream_t st) {
+  constexpr int G = 256 / (D / 4);
+  hipLaunchKernelGGL((k_bag_pieces<D, COMPACT>), dim3(grid_for(pieces_max(n_ids), G)), dim3(256),
+                     0, st, sv, w.pstart0, w.pseg0, b.uniq, w.totals, b.pos_bag, b.pos_coef,
+                     grad_out, grad_table, w.xp0);
+  NCF_CHECK_LAUNCH("ncf_bag_pool_bwd(pieces)");
+  hipLaunchKernelGGL((k_bag_combine<D, COMPACT>), dim3(grid_for(n_ids, G)), dim3(256), 0, st,
+                     w.fpiece0, b.uniq, w.totals, w.xp0, grad_table);
+  NCF_CHECK_LAUNCH("ncf_bag_pool_bwd(combine)");
+  return NCF_OK;
+}
+
 template <int D>
 int launch_bag_bwd(const int64_t* ids, int64_t n_ids, const BagWS& b, const float* table,
                    const float* grad_out, int64_t rows, float* grad_table, float* grad_weights,
-                   hipStream_t st) {
+                   bool compact, hipStream_t st) {
   const WS w = carve(b.dedup, n_ids, D);
   uint32_t *k0, *v0, *k1, *v1;
   sorted_bufs(w, sort_passes(rows, 1), &k0, &v0, &k1, &v1);
-  constexpr int G = 256 / (D / 4);
   if (grad_table) {
-    hipLaunchKernelGGL((k_bag_pieces<D>), dim3(grid_for(pieces_max(n_ids), G)), dim3(256), 0, st,
-                       v0, w.pstart0, w.pseg0, b.uniq, w.totals, b.pos_bag, b.pos_coef, grad_out,
-                       grad_table, w.xp0);
-    NCF_CHECK_LAUNCH("ncf_bag_pool_bwd(pieces)");
-    hipLaunchKernelGGL((k_bag_combine<D>), dim3(grid_for(n_ids, G)), dim3(256), 0, st, w.fpiece0,
-                       b.uniq, w.totals, w.xp0, grad_table);
-    NCF_CHECK_LAUNCH("ncf_bag_pool_bwd(combine)");
+    const int rc = compact
+        ? launch_bag_table_grad<D, true>(w, v0, b, n_ids, grad_out, grad_table, st)
+        : launch_bag_table_grad<D, false>(w, v0, b, n_ids, grad_out, grad_table, st);
+    if (rc != NCF_OK) return rc;
   }
   if (grad_weights) {
     hipLaunchKernelGGL((k_bag_grad_weights<D>), dim3(ncf_cdiv(n_ids * (D / 4), 256)), dim3(256), 0,
@@ -333,38 +363,55 @@ extern "C" int ncf_bag_pool_bwd(const int64_t* ids, int64_t n_ids, const int64_t
   NCF_CHECK_ARG(n_ids >= 0 && n_ids < (1ll << 30) && bags >= 0 && bags < (1ll << 31),
                 "ncf_bag_pool_bwd: bad n_ids / bags");
   NCF_CHECK_ARG(rows >= 0 && rows <= (1ll << 32), "ncf_bag_pool_bwd: rows must be in [0, 2^32]");
-  NCF_CHECK_ARG(mode == 0 || mode == 1, "ncf_bag_pool_bwd: mode must be 0 (sum) or 1 (mean)");
+  const bool compact = (mode & NCF_BAG_COMPACT) != 0;
+  mode &= ~NCF_BAG_COMPACT;
+  NCF_CHECK_ARG(mode == 0 || mode == 1,
+                "ncf_bag_pool_bwd: mode must be 0 (sum) or 1 (mean), NCF_BAG_COMPACT the only flag");
   NCF_CHECK_ARG(dim_ok(dim), "unsupported embedding dim %lld (16/32/64/128/256)", (long long)dim);
   NCF_CHECK_ARG(grad_weights == nullptr || (mode == 0 && (table || n_ids == 0)),
                 "ncf_bag_pool_bwd: grad_weights is for mode 0 (sum) and needs the table");
   NCF_CHECK_ARG(grad_table || grad_weights, "ncf_bag_pool_bwd: no gradient asked for");
+  NCF_CHECK_ARG(!compact || (grad_table && workspace),
+                "ncf_bag_pool_bwd: NCF_BAG_COMPACT needs grad_table and the workspace");
   hipStream_t st = (hipStream_t)stream;
-  if (grad_table && rows > 0 &&
+  const auto ws_short = [&]() {
+    if (workspace_bytes >= bag_ws_bytes(n_ids, dim)) return false;
+    ncf_set_error("ncf_bag_pool_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes,
+                  (long long)bag_ws_bytes(n_ids, dim));
+    return true;
+  };
+  // dense: the O(rows) zero-fill; compact: nothing but the rows of the unique ids is written
+  if (!compact && grad_table && rows > 0 &&
       hipMemsetAsync(grad_table, 0, (size_t)rows * dim * sizeof(float), st) != hipSuccess) {
     ncf_set_error("ncf_bag_pool_bwd: zero-fill of grad_table failed");
     return NCF_ERR_LAUNCH;
   }
   if (n_ids == 0 || rows == 0) {
+    if (compact) {   // U = 0 in the output block, nothing else
+      if (ws_short()) return NCF_ERR_WORKSPACE;
+      if (hipMemsetAsync((char*)workspace + NCF_BAG_WS_COUNT_OFFSET, 0, 2 * sizeof(uint32_t),
+                         st) != hipSuccess) {
+        ncf_set_error("ncf_bag_pool_bwd: zeroing the unique count failed");
+        return NCF_ERR_LAUNCH;
+      }
+    }
     if (grad_weights && n_ids > 0)
       (void)hipMemsetAsync(grad_weights, 0, (size_t)n_ids * sizeof(float), st);
     return NCF_OK;
   }
   NCF_CHECK_ARG(ids && offsets && (grad_out || bags == 0) && workspace,
                 "ncf_bag_pool_bwd: null pointer");
-  if (workspace_bytes < bag_ws_bytes(n_ids, dim)) {
-    ncf_set_error("ncf_bag_pool_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                  (long long)bag_ws_bytes(n_ids, dim));
-    return NCF_ERR_WORKSPACE;
-  }
+  if (ws_short()) return NCF_ERR_WORKSPACE;
   const BagWS b = bag_carve(workspace, n_ids, dim);
   if (grad_table) {
+    // (count[0] = U, count[1] = 0 for the empty second list: the head of the workspace)
     const int rc = ncf_dedup_ids2(ids, n_ids, rows, nullptr, 0, 1, dim, b.uniq, nullptr, nullptr,
-                                  nullptr, nullptr, b.dedup, b.dedup_bytes, stream);
+                                  nullptr, b.count, b.dedup, b.dedup_bytes, stream);
     if (rc != NCF_OK) return rc;
   }
   hipLaunchKernelGGL(k_bag_pos<>, dim3(ncf_cdiv(n_ids, 256)), dim3(256), 0, st, ids, n_ids,
                      offsets, bags, weights, rows, mode, b.pos_bag, b.pos_coef);
   NCF_CHECK_LAUNCH("ncf_bag_pool_bwd(positions)");
   NCF_BAG_DISPATCH_D(dim, launch_bag_bwd, ids, n_ids, b, table, grad_out, rows, grad_table,
-                     grad_weights, st);
+                     grad_weights, compact, st);
 }

@@ -32,6 +32,7 @@ receive materialised dense table gradients and run unchanged.
 """
 import weakref
 
+import numpy as np
 import torch
 import torch.optim.optimizer as _topt
 
@@ -471,3 +472,154 @@ def _pre_hook(opt, args, kwargs):
 
 def _post_hook(opt, args, kwargs):
     _restore_groups(opt)
+
+
+# ---- SparseAdam: the row-wise step of sparse (COO) table gradients ---------------------------
+TABLE_WIDTHS = (16, 32, 64, 128, 256)      # the widths the table kernels take (NCF_DISPATCH_DIM)
+_SPARSE_WINDOW = 256                       # steps of scalars uploaded at a time
+
+
+def sparse_step_scalars(lr, betas, eps, first, count):
+    """``[count, 4]`` fp32: the step-table entries that make ``ncf_adam_rows_apply`` (with
+    ``weight_decay = 0``) take torch.optim.SparseAdam's step ``first + i``.  The kernel's element
+    update is ``p += neg_step * m / (sqrt(v) * inv_bc + eps)`` (csrc/adam_math.h, adam1); torch's
+    SparseAdam puts both bias corrections into the step size and none under the root
+    (``p -= lr sqrt(1 - b2^t) / (1 - b1^t) * m / (sqrt(v) + eps)``), so
+    ``neg_step = -lr sqrt(1 - b2^t) / (1 - b1^t)`` and ``inv_bc = 1``; the other two floats are the
+    folded zero-gradient constants ``inv_bc / neg_step`` and ``eps / neg_step``, which the apply
+    does not read.  Computed in float64, rounded once."""
+    b1, b2 = betas
+    t = np.arange(first, first + count, dtype=np.float64)
+    ns = -(lr * np.sqrt(1.0 - np.power(b2, t)) / (1.0 - np.power(b1, t)))
+    out = np.empty((count, 4), dtype=np.float64)
+    out[:, 0], out[:, 1] = ns, 1.0
+    with np.errstate(divide="ignore"):
+        out[:, 2] = np.where(ns != 0.0, 1.0 / ns, -3.0e38)
+        out[:, 3] = np.where(ns != 0.0, eps / ns, -3.0e38)
+    return out.astype(np.float32)
+
+
+class SparseAdam(torch.optim.Optimizer):
+    """``torch.optim.SparseAdam`` for fp32 tables on the GPU, one launch per parameter.
+
+    Only the rows a coalesced sparse gradient names change: ``m += (1-b1)(g-m)``,
+    ``v += (1-b2)(g^2-v)``, ``p -= lr sqrt(1-b2^t)/(1-b1^t) m / (sqrt(v) + eps)``; no weight decay.
+    The step is ``ncf_adam_rows_apply`` (csrc/adam.hip), the touched-row apply of the deferred
+    table Adam, given the gradient's own index list and value rows, ``weight_decay = 0`` and a
+    step table in SparseAdam's form (``sparse_step_scalars``): no new kernel.  Against torch's
+    own it differs by rounding (explicit fmas, the hardware square root and reciprocal).
+
+    Takes what ``pool_rows(sparse=True)`` / ``EmbeddingBagCollection(sparse=True)`` produce (and
+    ``nn.Embedding(sparse=True)``): sparse fp32 CUDA gradients, one sparse dimension, of 2-d
+    contiguous fp32 parameters of width 16, 32, 64, 128 or 256.  A gradient that is not coalesced
+    is coalesced first (torch's sort); otherwise the launch is the step's only device work, save
+    the upload of the step scalars: 256 steps' worth (4 KB) every 256 steps while ``lr`` / ``betas``
+    / ``eps`` (read from the param group every step) stay as they are, one step's worth (32
+    bytes, a synchronous copy from the host) at a step that changes them, so under a scheduler
+    that moves ``lr`` every step, once per step.
+
+    Memory: the moments are dense ``[rows, dim]``, as torch.optim.SparseAdam's are, and the apply
+    kernel needs a row-stamp array the optimizer never reads: one ``int32 [rows]`` buffer per
+    parameter (4 bytes per row), allocated and zero-filled at its first step and kept outside
+    ``state``.  Nothing proportional to the table is allocated or written per step.
+
+    State is torch.optim.SparseAdam's (``step``, ``exp_avg``, ``exp_avg_sq``): a ``state_dict``
+    loads into a stock ``SparseAdam`` and back.  Refused, never run another way: a dense gradient
+    (RuntimeError, torch's message), ``maximize=True``, a parameter that is not 2-d fp32 of a
+    supported width (ValueError at construction), a parameter off the GPU or not contiguous, a
+    gradient with more than one sparse dimension."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, maximize=False):
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 < lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 < eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if maximize:
+            raise ValueError("ncf_amd.SparseAdam: maximize=True is not supported (negate the loss)")
+        # (the groups keep torch's keys, `maximize` included, so a state_dict moves both ways)
+        super().__init__(params, {"lr": lr, "betas": betas, "eps": eps, "maximize": False})
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.is_sparse:
+                    raise ValueError("SparseAdam requires dense parameter tensors")
+                if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] not in TABLE_WIDTHS:
+                    raise ValueError(
+                        f"ncf_amd.SparseAdam: parameters must be 2-d float32 tables of width "
+                        f"{'/'.join(map(str, TABLE_WIDTHS))}, not {p.dtype} {tuple(p.shape)}")
+        self._stamps = {}       # param -> int32 [rows]: the apply kernel's row stamps (scratch)
+        self._tables = {}       # (device, lr, betas, eps) -> (first step, steps, device table)
+
+    def _table_entry(self, device, lr, betas, eps, step):
+        """(device step table, index of ``step`` in it).  A table holds the scalars of the steps
+        first .. first + count - 1 of one (lr, betas, eps).  Hyperparameters seen for the first
+        time while others are in use (a scheduler changing ``lr`` every step) get a table of that
+        one step, 32 bytes; if they stay, the next step builds their full window.  At most 8
+        tables are kept, the oldest goes first."""
+        key = (device, lr, betas, eps)
+        c = self._tables.get(key)
+        if c is None or not c[0] <= step < c[0] + c[1]:
+            count = 1 if c is None and any(k[0] == device for k in self._tables) \
+                else _SPARSE_WINDOW
+            host = np.zeros((count + 1, 4), dtype=np.float32)              # (entry 0: unused)
+            host[1:] = sparse_step_scalars(lr, betas, eps, step, count)
+            self._tables.pop(key, None)
+            while len(self._tables) >= 8:
+                self._tables.pop(next(iter(self._tables)))
+            c = self._tables[key] = (step, count, torch.from_numpy(host).to(device))
+        return c[2], step - c[0] + 1
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            if group.get("maximize", False):
+                raise ValueError("ncf_amd.SparseAdam: maximize=True is not supported")
+            lr, eps = float(group["lr"]), float(group["eps"])
+            betas = (float(group["betas"][0]), float(group["betas"][1]))
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not g.is_sparse:
+                    raise RuntimeError("SparseAdam does not support dense gradients, please "
+                                       "consider Adam instead")
+                if p.device.type != "cuda" or not p.is_contiguous():
+                    raise RuntimeError("ncf_amd.SparseAdam: parameters must be contiguous CUDA "
+                                       "tensors (no CPU fallback)")
+                if g.dtype != torch.float32 or g.sparse_dim() != 1 or g.shape != p.shape:
+                    raise ValueError("ncf_amd.SparseAdam: the gradient must be float32 with one "
+                                     "sparse dimension (rows) and the parameter's shape")
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = 0
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["step"] += 1
+                if not g.is_coalesced():
+                    g = g.coalesce()      # (the update is not linear: every row once)
+                idx, vals = g._indices().contiguous(), g._values().contiguous()
+                n = vals.shape[0]
+                if n == 0:
+                    continue
+                m, v = state["exp_avg"], state["exp_avg_sq"]
+                if not (m.is_contiguous() and v.is_contiguous()):
+                    raise RuntimeError("ncf_amd.SparseAdam: exp_avg / exp_avg_sq must be contiguous")
+                stamp = self._stamps.get(p)
+                if stamp is None or stamp.device != p.device:
+                    stamp = self._stamps[p] = torch.zeros(p.shape[0], dtype=torch.int32,
+                                                          device=p.device)
+                table, at = self._table_entry(p.device, lr, betas, eps, int(state["step"]))
+                _lib.call("ncf_adam_rows_apply", ptr(p), ptr(m), ptr(v), ptr(vals),
+                          None, None, None, None, p.shape[1], ptr(idx), None, 0, n,
+                          ptr(stamp), at, ptr(table), betas[0], betas[1], eps, 0.0,
+                          _lib.stream_ptr(p.device))
+        return loss

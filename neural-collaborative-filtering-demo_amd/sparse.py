@@ -18,7 +18,11 @@ purchase history (up to 50 items per customer, src/data/training_data.py:72-81).
 Out of scope, and refused loudly: pooled bags through ``AdvancedNCF.forward`` /
 ``forward_simple`` / ``get_user_embeddings`` / ``get_product_embeddings`` (the reference's forward
 takes its batch size from ``values.size(0)``, architecture.py:274-276, and cannot take them
-either), sparse (COO) gradients, bf16 tables, a fused LayerNorm, row-sharded pooled lookups.
+either), bf16 tables, a fused LayerNorm, row-sharded pooled lookups.
+
+``sparse=True`` (``pool_rows`` and a free-standing collection) gives the table a coalesced sparse
+(COO) gradient of its touched rows, as ``nn.EmbeddingBag(sparse=True)`` does, for
+``ncf_amd.SparseAdam`` (optim.py) or ``torch.optim.SparseAdam``; the default stays dense.
 """
 import enum
 from dataclasses import dataclass, field
@@ -248,12 +252,17 @@ class EmbeddingBagCollection(nn.Module):
     free-standing collection.  A collection owned by an AdvancedNCF (one with ``set_sync``
     installed) returns tensors without ``grad_fn``, as its single-id forward does: the fused
     optimizer binding owns those tables' gradients.  The model's own forward keeps refusing
-    pooled bags.  Not provided: sparse (COO) gradients, bf16 tables, a fused LayerNorm,
-    row-sharded pooled lookups."""
+    pooled bags.  ``sparse=True``: the pooled path of a free-standing collection gives every
+    table a sparse (COO) gradient (``pool_rows(sparse=True)``); two features sharing a table add
+    two of them, and autograd's sum may be uncoalesced, as torch's own is.  The single-id gather
+    has no gradient and a model-owned collection produces none, so both ignore the flag.  Not
+    provided: bf16 tables, a fused LayerNorm, row-sharded pooled lookups."""
 
-    def __init__(self, tables: List[EmbeddingBagConfig], device=None, is_weighted: bool = False):
+    def __init__(self, tables: List[EmbeddingBagConfig], device=None, is_weighted: bool = False,
+                 sparse: bool = False):
         super().__init__()
         self._is_weighted = bool(is_weighted)
+        self._sparse = bool(sparse)
         self._embedding_bag_configs = list(tables)
         self.embedding_bags = nn.ModuleDict()
         for t in self._embedding_bag_configs:
@@ -326,7 +335,8 @@ class EmbeddingBagCollection(nn.Module):
                     with torch.no_grad():
                         out[f] = pool_rows(table.detach(), values[opk[i]:opk[i + 1]], off, w, mode)
                 else:
-                    out[f] = pool_rows(table, values[opk[i]:opk[i + 1]], off, w, mode)
+                    out[f] = pool_rows(table, values[opk[i]:opk[i + 1]], off, w, mode,
+                                       sparse=self._sparse)
         return out
 
     def set_sync(self, fn):
@@ -349,7 +359,8 @@ _MODES = {"sum": 0, "mean": 1}
 
 class _PoolRows(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, table, weights, ids, offsets, mode, check):
+    def forward(ctx, table, weights, ids, offsets, mode, check, sparse=False):
+        ctx.sparse = sparse
         t = table.detach()
         bags = offsets.numel() - 1
         out = torch.empty(bags, t.shape[1], device=t.device, dtype=torch.float32)
@@ -373,21 +384,38 @@ class _PoolRows(torch.autograd.Function):
         t, w, ids, offsets = ctx.saved_tensors
         need_t, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and w is not None
         if not (need_t or need_w):
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         g = grad_out.to(torch.float32).contiguous()
         n, bags, dim = ids.numel(), offsets.numel() - 1, t.shape[1]
-        gt = torch.empty_like(t) if need_t else None    # (zero-filled by the call)
+        compact = need_t and ctx.sparse
+        if compact:     # one row per unique id at most: O(n), whatever the table's height
+            gt = torch.empty(max(1, min(n, t.shape[0])), dim, device=t.device, dtype=torch.float32)
+        else:
+            gt = torch.empty_like(t) if need_t else None    # (zero-filled by the call)
         gw = torch.empty(n, device=t.device, dtype=torch.float32) if need_w else None
         ws = torch.empty(_lib.query("ncf_bag_pool_bwd_workspace", n, bags, dim), dtype=torch.uint8,
                          device=t.device)
+        mode = ctx.mode | (_lib.BAG_COMPACT if compact else 0)
         _lib.call("ncf_bag_pool_bwd", _lib.ptr(ids), n, _lib.ptr(offsets), bags, _lib.ptr(w),
-                  _lib.ptr(t) if need_w else None, _lib.ptr(g), t.shape[0], dim, ctx.mode,
+                  _lib.ptr(t) if need_w else None, _lib.ptr(g), t.shape[0], dim, mode,
                   _lib.ptr(gt), _lib.ptr(gw), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(t.device))
-        return gt, gw, None, None, None, None
+        if compact:
+            # the call's output block at the head of its workspace (include/ncf_hip.h): the one
+            # host read of the sparse backward, then copies of the U ids so the workspace goes
+            c0, i0 = _lib.BAG_WS_COUNT_OFFSET, _lib.BAG_WS_IDS_OFFSET
+            u = int(ws[c0:c0 + 4].view(torch.int32).item())
+            idx = ws[i0:i0 + 8 * u].view(torch.int64).clone().unsqueeze(0)
+            gt = torch.sparse_coo_tensor(idx, gt[:u], t.shape, is_coalesced=True)
+            # A sparse gradient that autograd's AccumulateGrad can steal is rebuilt there from its
+            # indices and values without the coalesced flag; one that is referenced elsewhere is
+            # cloned, flag kept (and to exactly U rows).  Hold it until the graph goes, so that
+            # ``table.grad.is_coalesced()``.
+            ctx.keep = gt
+        return gt, gw, None, None, None, None, None
 
 
 def pool_rows(table: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, weights=None,
-              mode: str = "sum", check: bool = True) -> torch.Tensor:
+              mode: str = "sum", check: bool = True, sparse: bool = False) -> torch.Tensor:
     """HIP pooled lookup, the functional form beside ``gather_rows``:
     ``out[b] = scale_b * sum_{p in [offsets[b], offsets[b+1])} weights[p] * table[ids[p]]`` for
     ``offsets`` of ``bags + 1`` entries relative to ``ids`` (``nn.functional.embedding_bag`` with
@@ -399,8 +427,19 @@ def pool_rows(table: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, wei
     Differentiable: the gradient to ``table`` is dense ``[rows, dim]`` (what torchrec's unsharded
     EBC / ``nn.EmbeddingBag(sparse=False)`` produce), bitwise reproducible (no float atomics; one
     id's terms are added in sorted-position order, in chunks of ``BAG_BWD_CHUNK``); ``weights``
-    get theirs when they require grad; only what is asked for is computed.  No sparse (COO)
-    gradients, no bf16 tables, no fused LayerNorm.
+    get theirs when they require grad; only what is asked for is computed.  No bf16 tables, no
+    fused LayerNorm.
+
+    ``sparse=True`` (``nn.EmbeddingBag(sparse=True)``): the gradient to ``table`` is a coalesced
+    ``torch.sparse_coo_tensor`` of ``table.shape`` instead: indices ``[1, U]``, the unique ids
+    ascending, values ``[U, dim]``, row for row the bits the dense gradient holds there
+    (``grad.to_dense()`` is the dense path's gradient bitwise).  The backward then touches memory
+    proportional to ``ids.numel()`` and never to the table's height (no ``[rows, dim]`` buffer,
+    no zero-fill), and reads ``U`` from the device once per backward, whatever ``check`` is.  An
+    id none of whose positions lies in a bag is listed with a zero row; an id out of range
+    (``check=False``) is not listed, and makes row 0 listed (a zero row unless real positions name
+    it).  Everything else is as without it.  ``ncf_amd.SparseAdam`` and
+    ``torch.optim.SparseAdam`` step such gradients.
 
     ``check=True`` reads the kernel's flag once: IndexError for an id outside the table,
     ValueError for offsets that decrease or leave ``[0, ids.numel()]`` (the kernel clamps: nothing
@@ -424,7 +463,8 @@ def pool_rows(table: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, wei
         weights = weights.to(device=table.device, dtype=torch.float32).contiguous()
         if weights.numel() != ids.numel():
             raise ValueError("pool_rows: one weight per id")
-    return _PoolRows.apply(table, weights, ids.reshape(-1), offsets, _MODES[mode], bool(check))
+    return _PoolRows.apply(table, weights, ids.reshape(-1), offsets, _MODES[mode], bool(check),
+                           bool(sparse))
 
 
 def gather_rows(table: torch.Tensor, ids: torch.Tensor, gamma=None, beta=None, eps=1e-5) -> torch.Tensor:
